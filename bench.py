@@ -2,7 +2,12 @@
 """Headline benchmark: 640x480 depth frames/s fused into a 5 cm TSDF submap per MI355X (BASELINE.json configs[1]) +
 submap registrations/s, one coxgraph client per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps of the headline and prints its line (`value`, `ms_per_step`); every other block
+described below (the instrumented passes and `roofline`, `other_methods`, `other_configs`, `pcie_inclusive`, `registration`,
+`distributed_registration`, `cpu_baseline`) is measured only with `--full` and is null otherwise.  `--dump-outputs DIR` writes the
+layer the timed steps fused (see dump_layer) as .npy files, so that two builds can be compared output for output.
 
 A "step" is one pass of the hot path over one synthetic depth frame: integratePointCloud(T_G_C, points_C, colors) of
 307 200 points into the client's submap layer, inputs already resident in HBM.  The reference configures two integrators on
@@ -35,6 +40,7 @@ import os
 import subprocess
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -73,6 +79,9 @@ def parse():
     ap.add_argument("--no-profile-pass", action="store_true")
     ap.add_argument("--serial", action="store_true", help="sync after every frame (profiling aid: kernel times without cross-frame overlap)")
     ap.add_argument("--no-ramp", action="store_true", help="no untimed clock-ramp frames (PMC passes: every dispatch of the run then belongs to warmup + steps frames)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: instrumented passes + roofline, the other methods and "
+                                                        "configs, PCIe-inclusive legs, registration, CPU baseline (the options above that bound them apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the layer they fused to DIR/<name>.npy (dump_layer)")
     return ap.parse_args()
 
 
@@ -128,6 +137,26 @@ def pmc_traffic(method):
         return None, {"source": None, "note": "no PMC summary committed for this method yet"}
 
 
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_layer(layer, out_dir):
+    """What a caller of the timed path reads back, the fused layer (cox_layer_download, blocks sorted by (z, y, x)), as float arrays:
+    block_index [n, 3] of every block, and for the blocks listed in voxel_block_index [m, 3] their voxels' tsdf_distance [m, 4096],
+    tsdf_weight [m, 4096] and color [m, 4096, 4] (RGBA 0-255).  m = n unless that exceeds DUMP_BYTES in all; then the blocks are a
+    fixed, seeded sample (seed 0) of the n."""
+    from coxgraph_amd.capi import VOXELS_PER_BLOCK, words_to_fields
+    idx, vox = layer.download()
+    n = len(idx)
+    m = min(n, (DUMP_BYTES - 2 * idx.size * 8) // (VOXELS_PER_BLOCK * (4 + 4 + 4 * 4)))
+    rows = np.arange(n) if m == n else np.sort(np.random.default_rng(0).choice(n, m, replace=False))
+    d, w, rgba = words_to_fields(vox[rows])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("block_index", idx.astype(np.float64)), ("voxel_block_index", idx[rows].astype(np.float64)), ("tsdf_distance", d),
+                    ("tsdf_weight", w), ("color", rgba.astype(np.float32))):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -174,18 +203,24 @@ def main():
     if (W, H) not in synth.INTRINSICS:
         raise SystemExit(f"bench.py: no intrinsics for {W}x{H} (have {sorted(synth.INTRINSICS)})")
     n_frames = args.warmup + args.steps
-    keep_host = max(args.cpu_frames, (args.warmup + args.steps) if args.pcie_frames < 0 else (args.warmup + args.pcie_frames if args.pcie_frames else 0), 1)
+    keep_host = 0  # host copies of the frames: only the PCIe-inclusive legs and the CPU baseline (--full) read them
+    if args.full:
+        keep_host = max(args.cpu_frames, (args.warmup + args.steps) if args.pcie_frames < 0 else (args.warmup + args.pcie_frames if args.pcie_frames else 0), 1)
 
     def make_frames(n, w, h, keep):
         """-> (host frames (the first `keep`), device-resident frames)"""
-        host, dev = [], []
-        for t in range(n):
+        def render(t):
             # one client per GPU; with several clients they stand 30 degrees apart on the camera circle, so that neighbouring
             # clients' submaps overlap and the inter-robot constraints have correspondences
-            T, pts, rgba, depth = synth.make_frame(t, client=rank, n_clients=(12 if world > 1 else 1), w=w, h=h)
-            if t < keep:
-                host.append((T, pts, rgba, depth))
-            dev.append((T, torch.from_numpy(pts).cuda(), torch.from_numpy(rgba).cuda(), pts.shape[0]))
+            return synth.make_frame(t, client=rank, n_clients=(12 if world > 1 else 1), w=w, h=h)
+        host, dev = [], []
+        # ~50-80 ms of numpy per 640x480 frame, most of it in array arithmetic that releases the GIL: frames are rendered by a few
+        # threads (at most the 16 CPUs a process may use, shared by the ranks) and uploaded in order as they come
+        with ThreadPoolExecutor(max(1, min(16, os.cpu_count() or 1) // world)) as pool:
+            for t, (T, pts, rgba, depth) in enumerate(pool.map(render, range(n))):
+                if t < keep:
+                    host.append((T, pts, rgba, depth))
+                dev.append((T, torch.from_numpy(pts).cuda(), torch.from_numpy(rgba).cuda(), pts.shape[0]))
         torch.cuda.synchronize()
         return host, dev
 
@@ -323,14 +358,17 @@ def main():
         return layer, integ, dt, out
 
     # ---- headline ----------------------------------------------------------------------------------------------------
-    layer, integ, dt, head = measure(args.method, args.steps, args.warmup, dev_frames, cfg, args.voxel, profile=not args.no_profile_pass, events=not args.no_events)
+    layer, integ, dt, head = measure(args.method, args.steps, args.warmup, dev_frames, cfg, args.voxel, profile=args.full and not args.no_profile_pass,
+                                     events=not args.no_events)
+    if args.dump_outputs and rank == 0:
+        dump_layer(layer, args.dump_outputs)
     fps = head["value"]
     host_ms = head["host_submit_ms_per_frame"]
     roofline, frame_stats, crit = head.get("roofline"), head.get("frame_stats_mean"), head.get("critical_path")
 
     # ---- the other method on the same stream, as a block of its own -------------------------------------------------------
     other = None
-    if rank == 0 and world == 1 and args.other_frames > 0 and args.method in ("fast", "merged"):
+    if args.full and rank == 0 and world == 1 and args.other_frames > 0 and args.method in ("fast", "merged"):
         om = "merged" if args.method == "fast" else "fast"
         nf = min(args.other_frames, args.steps)
         _, _, _, blk = measure(om, nf, args.warmup, dev_frames, cfg, args.voxel, profile=not args.no_profile_pass, events=not args.no_events)
@@ -369,7 +407,7 @@ def main():
 
     # ---- the other shapes BASELINE.json names, short and bounded, each with a roofline of its own ---------------------------------
     other_configs = None
-    if rank == 0 and world == 1 and args.other_config_frames > 0 and abs(args.voxel - 0.05) < 1e-9 and (W, H) == (640, 480):
+    if args.full and rank == 0 and world == 1 and args.other_config_frames > 0 and abs(args.voxel - 0.05) < 1e-9 and (W, H) == (640, 480):
         other_configs = {}
         ocf, ocw = args.other_config_frames, 6
         for name, (w2, h2, vox2) in (("configs[3]: 1280x720, 2 cm (coxgraph/config/tsdf_server_rs.yaml:12-17)", (1280, 720, 0.02)),
@@ -399,7 +437,7 @@ def main():
     # Every leg repeats the resident run with another entry point: the same frames (warm-up, then `steps` timed), a fresh layer, the
     # clock ramp; `--pcie-frames` bounds the timed frames (default: all of them).
     pcie = None
-    if rank == 0 and world == 1 and args.pcie_frames != 0:
+    if args.full and rank == 0 and world == 1 and args.pcie_frames != 0:
         nw = min(args.warmup, len(host_frames))
         nf = min(args.steps if args.pcie_frames < 0 else min(args.pcie_frames, args.steps), len(host_frames) - nw)
         pcie = {"frames": nf, "warmup": nw, "bytes_per_frame_points": int(host_frames[0][1].nbytes + host_frames[0][2].nbytes),
@@ -492,7 +530,7 @@ def main():
     reg = None
     trunc = cfg.default_truncation_distance
     esdf_cfg = dict(max_distance_m=2.0, min_distance_m=0.5 * trunc)
-    if rank == 0 and world == 1 and args.reg_iters > 0:  # (N > 1: the inter-robot leg below is the registration measurement)
+    if args.full and rank == 0 and world == 1 and args.reg_iters > 0:  # (N > 1: the inter-robot leg below is the registration measurement)
         from coxgraph_amd.posegraph import PoseGraphInterface
         m3 = max(1, len(dev_frames) // 3)
         subs = []
@@ -566,7 +604,7 @@ def main():
 
     # ---- N > 1: submap exchange + inter-robot registration ------------------------------------------------------------------
     dist_reg = None
-    if world > 1 and args.reg_iters > 0:
+    if args.full and world > 1 and args.reg_iters > 0:
         from coxgraph_amd.posegraph import PoseGraph, RegistrationConstraint
         # finishSubmap() on the client's own GPU
         ref = RegPoints.from_isosurface(eng, layer, 1.0)
@@ -666,7 +704,7 @@ def main():
 
     # ---- CPU baseline on rank 0, N = 1 only ---------------------------------------------------------------
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_frames > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_frames > 0:
         threads = min(8, os.cpu_count() or 1)
         res = cpu_baseline([f[:3] for f in host_frames], args.voxel, min(args.cpu_frames, len(host_frames)), threads)
         cpu = {"value": res["fast"][0], "unit": "frames/s", "cores": threads, "kind": "port",
