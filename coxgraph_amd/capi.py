@@ -678,6 +678,109 @@ class MeshConverter:
         return int(nr.value), int(ni.value)
 
 
+COLOR_MODES = {"color": 0, "normals": 1, "gray": 2, "lambert": 3, "lambert_color": 4}
+
+
+class MeshLayer:
+    """voxblox::MeshLayer of a TSDF layer (cox_meshlayer_t, include/coxgraph_hip_mesh.h): per block with triangles its index and
+    vertex range; per vertex position, face normal and colour; triangle t = vertices 3t, 3t+1, 3t+2."""
+
+    def __init__(self, eng, h):
+        self.eng, self.h = eng, h
+        nb, nv, edge = C.c_uint64(), C.c_uint64(), C.c_float()
+        eng.check(eng.fn("meshlayer_size")(self.h, C.byref(nb), C.byref(nv), C.byref(edge)), "meshlayer_size")
+        self.n_blocks, self.n_vertices, self.block_edge_length = int(nb.value), int(nv.value), float(edge.value)
+        self.n_triangles = self.n_vertices // 3
+
+    @classmethod
+    def from_layer(cls, eng, layer, min_weight=1e-4):
+        """MeshIntegrator::generateMesh over the whole layer (corners valid when weight > min_weight)."""
+        h = C.c_void_p()
+        eng.check(eng.fn("meshlayer_from_layer")(layer.h, C.c_float(min_weight), C.byref(h), None, None), "meshlayer_from_layer")
+        return cls(eng, h)
+
+    def close(self):
+        if self.h:
+            self.eng.fn("meshlayer_destroy", None)(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def stats(self):
+        """(vertices whose colour voxel lay in no block, (count kernel ms, write kernel ms))."""
+        n, ms = C.c_uint64(), np.zeros(2, np.float64)
+        self.eng.check(self.eng.fn("meshlayer_stats")(self.h, C.byref(n), _fp(ms)), "meshlayer_stats")
+        return int(n.value), (float(ms[0]), float(ms[1]))
+
+    def download(self):
+        """dict(block_index int32[nb,3], vertex_begin uint64[nb+1], xyz float32[nv,3], normals float32[nv,3], rgb uint8[nv,3])."""
+        nb, nv = self.n_blocks, self.n_vertices
+        out = dict(block_index=np.zeros((nb, 3), np.int32), vertex_begin=np.zeros(nb + 1, np.uint64), xyz=np.zeros((nv, 3), np.float32),
+                   normals=np.zeros((nv, 3), np.float32), rgb=np.zeros((nv, 3), np.uint8))
+        self.eng.check(self.eng.fn("meshlayer_download")(self.h, *[_fp(out[k]) for k in ("block_index", "vertex_begin", "xyz", "normals", "rgb")],
+                                                         C.c_uint64(nb), C.c_uint64(nv)), "meshlayer_download")
+        return out
+
+    def data_ptr(self):
+        """(xyz, normals, rgb) device pointers as ints, and the vertex count."""
+        p, q, r, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self.eng.check(self.eng.fn("meshlayer_data_dev")(self.h, C.byref(p), C.byref(q), C.byref(r), C.byref(n)), "meshlayer_data_dev")
+        return int(p.value or 0), int(q.value or 0), int(r.value or 0), int(n.value)
+
+    def transform(self, T):
+        """In place: positions T p, normals R n (T = qw qx qy qz tx ty tz)."""
+        T = np.ascontiguousarray(T, np.float32)
+        assert T.shape == (7,)
+        self.eng.check(self.eng.fn("meshlayer_transform")(self.h, _fp(T)), "meshlayer_transform")
+
+    def msg_arrays(self, color_mode="color"):
+        """generateVoxbloxMeshMsg's per-vertex arrays: dict(x, y, z uint16[nv], r, g, b uint8[nv])."""
+        nv = self.n_vertices
+        out = {k: np.zeros(nv, np.uint16) for k in "xyz"}
+        out.update({k: np.zeros(nv, np.uint8) for k in "rgb"})
+        self.eng.check(self.eng.fn("meshlayer_msg")(self.h, C.c_int(COLOR_MODES[color_mode]), *[_fp(out[k]) for k in "xyzrgb"], C.c_uint64(nv)),
+                       "meshlayer_msg")
+        return out
+
+    def to_msg(self, color_mode="color", history=None, trajectory=()):
+        """A voxblox_msgs/Mesh in the dict form MeshMsg takes: MeshMsg(**mesh.to_msg(...)).  history: None, or a callable
+        (block index tuple, n_triangles) -> one run-length list per triangle (the caller's observation histories)."""
+        d = self.download()
+        a = self.msg_arrays(color_mode)
+        vb = d["vertex_begin"].astype(np.int64)
+        blocks = []
+        for k in range(self.n_blocks):
+            s, e = vb[k], vb[k + 1]
+            idx = tuple(int(v) for v in d["block_index"][k])
+            blk = dict(index=idx, **{c: a[c][s:e] for c in "xyzrgb"})
+            if history is not None:
+                blk["history"] = history(idx, int(e - s) // 3)
+            blocks.append(blk)
+        return dict(block_edge_length=self.block_edge_length, blocks=blocks, trajectory=list(trajectory))
+
+    @staticmethod
+    def connected(eng, parts, T_per_part=None, proximity_threshold=1e-4):
+        """createConnectedMesh of several meshes, each moved by its T first: dict(xyz, normals, rgb, triangles uint32[nt,3])."""
+        arr = (C.c_void_p * max(1, len(parts)))(*[p.h.value for p in parts])
+        T = None if T_per_part is None else np.ascontiguousarray(np.asarray(T_per_part, np.float32).reshape(len(parts), 7))
+        h, nv, nt = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        eng.check(eng.fn("meshlayer_connected")(arr, _fp(T) if T is not None else None, C.c_uint64(len(parts)), C.c_float(proximity_threshold),
+                                                C.byref(h), C.byref(nv), C.byref(nt)), "meshlayer_connected")
+        try:
+            nv, nt = int(nv.value), int(nt.value)
+            out = dict(xyz=np.zeros((nv, 3), np.float32), normals=np.zeros((nv, 3), np.float32), rgb=np.zeros((nv, 3), np.uint8),
+                       triangles=np.zeros((nt, 3), np.uint32))
+            eng.check(eng.fn("meshconn_download")(h, *[_fp(out[k]) for k in ("xyz", "normals", "rgb", "triangles")], C.c_uint64(nv), C.c_uint64(nt)),
+                      "meshconn_download")
+        finally:
+            eng.fn("meshconn_destroy", None)(h)
+        return out
+
+
 # ---- wire-format helpers (voxblox_msgs/Block data words) -----------------------------------------
 def words_to_fields(vox):
     """uint32[...,3] wire words -> (distance f32, weight f32, rgba u8[...,4])."""
