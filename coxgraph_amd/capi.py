@@ -16,6 +16,8 @@ STATUS = {
     -7: "COX_ERR_BUFFER_TOO_SMALL", -8: "COX_ERR_INTERNAL",
 }
 METHODS = {"simple": 0, "merged": 1, "fast": 2, "projective": 3}
+QUERY_MODES = {"nearest": 0, "interpolate": 1, "adaptive": 2}  # cox_query_mode (include/coxgraph_hip_map.h)
+Q_VALUE, Q_TRILINEAR, Q_GRADIENT = 1, 2, 4
 VOXELS_PER_BLOCK = 4096
 
 
@@ -213,6 +215,47 @@ class Layer:
         assert vox.shape == (idx.shape[0], VOXELS_PER_BLOCK, 3)
         self.eng.check(self.eng.fn("layer_upload")(self.h, _fp(idx), _fp(vox), C.c_uint64(idx.shape[0]), C.c_int(action)),
                        "layer_upload")
+
+    # ---- map queries (include/coxgraph_hip_map.h) ----
+    def query(self, xyz, mode="interpolate", gradient=False):
+        """voxblox Interpolator / EsdfMap batch queries at float32 points [n,3] in the layer's frame (cox_layer_query):
+        dict(distance[n], weight[n], [gradient[n,3],] status[n] uint8 of Q_VALUE | Q_TRILINEAR | Q_GRADIENT); NaN where the
+        matching status bit is clear."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        out = dict(distance=np.empty(n, np.float32), weight=np.empty(n, np.float32), status=np.empty(n, np.uint8))
+        if gradient:
+            out["gradient"] = np.empty((n, 3), np.float32)
+        self.eng.check(self.eng.fn("layer_query")(self.h, _fp(xyz), C.c_uint64(n), C.c_int(QUERY_MODES[mode]), C.c_int(int(gradient)),
+                                                  _fp(out["distance"]), _fp(out["weight"]), _fp(out["gradient"]) if gradient else None,
+                                                  _fp(out["status"])), "layer_query")
+        return out
+
+    def query_dev(self, xyz, n=None, mode="interpolate", gradient=False, distance=None, weight=None, grad=None, status=None, stream=None):
+        """cox_layer_query_dev: torch tensors on the layer's GPU or raw device pointers (ints; then n is required), enqueued on
+        `stream` (a torch stream, a raw hipStream_t or None = the null stream), not waited for.  Outputs left as they were
+        where a status bit is clear."""
+        def ptr(t):
+            if t is None:
+                return None
+            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        if n is None:
+            n = xyz.numel() // 3
+        s = getattr(stream, "cuda_stream", stream)
+        self.eng.check(self.eng.fn("layer_query_dev")(self.h, ptr(xyz), C.c_uint64(n), C.c_int(QUERY_MODES[mode]), C.c_int(int(gradient)), ptr(distance),
+                                                      ptr(weight), ptr(grad), ptr(status), C.c_void_p(s or 0)), "layer_query_dev")
+
+    def free_points(self, min_distance):
+        """createFreePointcloudFromEsdfLayer: (xyz float32[n,3] voxel centres, intensity float32[n] distances), blocks in download
+        order, voxels in linear index order."""
+        f = self.eng.fn("layer_free_points")
+        n = C.c_uint64()
+        self.eng.check(f(self.h, C.c_float(min_distance), None, None, C.c_uint64(0), C.byref(n)), "layer_free_points(query)")
+        xyz = np.zeros((int(n.value), 3), np.float32)
+        inten = np.zeros(int(n.value), np.float32)
+        if n.value:
+            self.eng.check(f(self.h, C.c_float(min_distance), _fp(xyz), _fp(inten), C.c_uint64(n.value), C.byref(n)), "layer_free_points")
+        return xyz, inten
 
 
 class Integrator:

@@ -20,16 +20,11 @@
 #include "../../include/coxgraph_hip.h"
 #include "cox_device.hpp"
 #include "cox_internal.hpp"
+#include "cox_interp.hpp"
 
 using namespace cox;
 
-struct ReadingView {
-  const u32* voxels;
-  const u64* ht_keys;
-  const u32* ht_vals;
-  u32 ht_mask;
-  float voxel_size, voxel_size_inv, block_size, block_size_inv;
-};
+using ReadingView = LayerView;
 
 // relative pose reading<-reference: float for the per-point transform, double for the Jacobians
 struct RelPose {
@@ -59,10 +54,6 @@ static RelPose make_rel_pose(const double ref[4], const double read[4]) {
   return P;
 }
 
-__constant__ float c_interp_table[8][8] = {{1, 0, 0, 0, 0, 0, 0, 0},   {-1, 0, 0, 0, 1, 0, 0, 0},   {-1, 0, 1, 0, 0, 0, 0, 0},
-                                           {-1, 1, 0, 0, 0, 0, 0, 0},  {1, 0, -1, 0, -1, 0, 1, 0},  {1, -1, -1, 1, 0, 0, 0, 0},
-                                           {1, -1, 0, 0, -1, 1, 0, 0}, {-1, 1, 1, -1, 1, -1, -1, 1}};
-
 struct PointResult {
   double r;
   double J[8];  // J_ref(4), J_read(4), unscaled
@@ -85,84 +76,14 @@ __device__ __forceinline__ PointResult reg_point(const ReadingView& L, const Rel
 #pragma unroll
   for (int k = 0; k < 3; ++k) sc[k] = pos[k] * L.block_size_inv;
   if (!(index_in_range(sc[0]) && index_in_range(sc[1]) && index_in_range(sc[2]))) return o;
-  int b[3], vi[3];
+  int b[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) b[k] = grid_index(sc[k]);
   if (ht_find(L.ht_keys, L.ht_mask, pack_key(b[0], b[1], b[2])) == kInvalid) return o;  // block of the point must exist
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float origin = static_cast<float>(b[k]) * L.block_size;
-    const float rel = pos[k] - origin;
-    int v = grid_index(rel * L.voxel_size_inv);
-    v = v > 15 ? 15 : (v < 0 ? 0 : v);
-    const float c = origin + center_coord(v, L.voxel_size);
-    if (pos[k] - c < 0.0f) {
-      v--;
-      if (v < 0) {
-        b[k]--;
-        v += 16;
-      }
-    }
-    vi[k] = v;
-  }
-  const u32 base_slot = ht_find(L.ht_keys, L.ht_mask, pack_key(b[0], b[1], b[2]));
-  if (base_slot == kInvalid) return o;
-  const u32 base_pool = L.ht_vals[base_slot];
-  if (base_pool == kInvalid) return o;
-  float d[8], off[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float c0 = static_cast<float>(b[k]) * L.block_size + center_coord(vi[k], L.voxel_size);
-    off[k] = (pos[k] - c0) * L.voxel_size_inv;
-  }
-  // the 8 neighbours: at most 8 blocks, one per corner of the 2x2x2 cell; resolve the (up to 7) other blocks first, then issue
-  // all 16 voxel loads independently of each other (the early-outs of a straight transcription serialise them)
-  u32 pools[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const int mx = (c >> 2) & 1, my = (c >> 1) & 1, mz = c & 1;
-    const bool need = (!mx || vi[0] == 15) && (!my || vi[1] == 15) && (!mz || vi[2] == 15);  // this block combination is touched
-    u32 pool = base_pool;
-    if (c != 0) {
-      pool = kInvalid;
-      if (need) {
-        const u32 slot = ht_find(L.ht_keys, L.ht_mask, pack_key(b[0] + mx, b[1] + my, b[2] + mz));
-        if (slot != kInvalid) pool = L.ht_vals[slot];
-      }
-    }
-    pools[c] = pool;
-  }
-  float wv[8];
-  bool all_blocks = true;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    int v[3] = {vi[0] + ((i >> 2) & 1), vi[1] + ((i >> 1) & 1), vi[2] + (i & 1)};
-    int sel = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      if (v[k] >= 16) {
-        v[k] -= 16;
-        sel |= 4 >> k;
-      }
-    const u32 pool = pools[sel];
-    all_blocks = all_blocks && pool != kInvalid;
-    const u32 safe = pool == kInvalid ? base_pool : pool;
-    const u32* vox = L.voxels + (static_cast<size_t>(safe) * kVoxelsPerBlock + static_cast<u32>(v[0] + 16 * (v[1] + 16 * v[2]))) * kWordsPerVoxel;
-    d[i] = __uint_as_float(vox[0]);
-    wv[i] = __uint_as_float(vox[1]);
-  }
-  if (!all_blocks) return o;
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-    if (!(wv[i] > 0.0f)) return o;  // Interpolator<TsdfVoxel>::isVoxelValid
+  float d[8], wv[8], off[3];
+  if (!interp_cell(L, pos, b, HtPool{L}, d, wv, off)) return o;
   float md[8];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    float s = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) s += c_interp_table[r][c] * d[c];
-    md[r] = s;
-  }
+  interp_table_apply(d, md);
   const float dx = off[0], dy = off[1], dz = off[2];
   const float q[8] = {1.0f, dx, dy, dz, dx * dy, dy * dz, dz * dx, dx * dy * dz};
   const float qx[8] = {0, 1, 0, 0, dy, 0, dz, dy * dz};
