@@ -2349,9 +2349,10 @@ static int integrate_device(cox_integrator* I, const float T[7], const float* xy
     if (I->submitter) I->submitter->wait_outstanding(1);
     I->host_wait_ns += static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - w0).count());
   }
+  // (first: a projective integrator that wrote last settles its frames here and may grow the layer, which follow_layer picks up)
+  const bool foreign_writer = (n != 0 || I->method == COX_METHOD_FAST) && cox_layer_order_writer(Lh, I);
   COX_TRY(ensure_capacity(I, n));
   COX_TRY(follow_layer(I));
-  const bool foreign_writer = (n != 0 || I->method == COX_METHOD_FAST) && cox_layer_order_writer(Lh, I);
   I->last = cox_frame_stats{};
   I->last.n_points = n;
   I->last_has_counts = false;

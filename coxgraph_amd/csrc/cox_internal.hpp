@@ -68,6 +68,11 @@ struct cox_layer {
   // (cox_layer_order_writer), so the frames of different integrators reach the layer in call order, as they do in voxblox, and the
   // last recorded event stands for every frame before it.
   const void* last_writer = nullptr;
+  // A projective integrator may find, only after the fact, that a frame it has enqueued ran out of pool; that frame is dropped whole
+  // on the device and enqueued again by the host (cox_projective.hip).  Nobody else may write the layer in between: the writer that
+  // takes over first lets the projective integrator settle its frames (settle_ctx is that integrator while it wrote last).
+  void (*settle_writer)(void* ctx) = nullptr;
+  void* settle_ctx = nullptr;
 };
 
 // make stream s wait for every frame enqueued so far on the layer (no-op when nothing was enqueued)
@@ -75,15 +80,22 @@ static inline void cox_layer_wait_writes(const cox_layer* L, hipStream_t s) {
   if (L->has_write && L->last_write) (void)hipStreamWaitEvent(s, L->last_write, 0);
 }
 int cox_internal_layer_reserve(cox_layer* L, u64 capacity_blocks);
+// the hash table again from the first n_blocks pool blocks, which become the layer's block count (device idle; same capacity)
+int cox_internal_layer_rebuild_table(cox_layer* L, u32 n_blocks);
 void cox_drain_submitters();
 // Called by an integrator's entry point before it enqueues a frame: true when another integrator wrote the layer last -- its
 // submission thread has then enqueued (and recorded last_write behind) everything it was handed, and the caller makes the
 // stream of its first layer-touching stage wait for last_write.
 static inline bool cox_layer_order_writer(cox_layer* L, const void* writer) {
-  const bool foreign = L->last_writer != nullptr && L->last_writer != writer && L->has_write;
-  if (foreign) cox_drain_submitters();
+  // has_write is set by the other integrator's submission thread once it has enqueued its frame: it is read only after that
+  // thread has been drained (a frame issued right after another integrator's very first asynchronous frame used to see it unset)
+  const bool foreign = L->last_writer != nullptr && L->last_writer != writer;
+  if (foreign) {
+    cox_drain_submitters();
+    if (L->settle_writer && L->settle_ctx == L->last_writer) L->settle_writer(L->settle_ctx);  // may grow the layer: callers re-read it after this
+  }
   L->last_writer = writer;
-  return foreign;
+  return foreign && L->has_write;
 }
 
 // voxgraph registration point set of a submap, resident on one GPU

@@ -440,6 +440,20 @@ int cox_internal_layer_reserve(cox_layer* L, u64 capacity_blocks) {
   return COX_OK;
 }
 
+int cox_internal_layer_rebuild_table(cox_layer* L, u32 n_blocks) {
+  if (n_blocks > L->capacity) return COX_ERR_INVALID_ARG;
+  COX_HIP(hipDeviceSynchronize());
+  COX_HIP(hipMemset(L->ht_keys, 0xFF, sizeof(u64) * L->ht_cap));
+  COX_HIP(hipMemset(L->ht_vals, 0xFF, sizeof(u32) * L->ht_cap));
+  COX_HIP(hipMemset(L->ht_stamp, 0, sizeof(u32) * L->ht_cap));
+  COX_HIP(hipMemset(L->ht_ord, 0, sizeof(u32) * L->ht_cap));
+  COX_HIP(hipMemcpy(L->d_nblocks, &n_blocks, sizeof(u32), hipMemcpyHostToDevice));
+  if (n_blocks) hipLaunchKernelGGL(k_rehash, dim3((n_blocks + 255) / 256), dim3(256), 0, nullptr, L->block_keys, n_blocks, L->ht_keys, L->ht_vals, L->ht_cap - 1, L->d_err);
+  COX_HIP(hipDeviceSynchronize());
+  *L->h_nblocks = n_blocks;
+  return COX_OK;
+}
+
 extern "C" int cox_layer_reserve(cox_layer_t* L, uint64_t capacity_blocks) {
   COX_ENTRY();
   if (!L) return COX_ERR_INVALID_ARG;

@@ -37,9 +37,11 @@ struct ProjParams {
   int rows, cols, scheme;
   int use_const_weight, carving, use_dropoff, deintegrate;
   u32 n_points, frame_id;
+  u32 seq;  // 1 + this integrator's own frame count: what a frame that runs out of pool leaves in the stall word
 };
 struct ProjCounters {
-  u32 n_touched, n_new_blocks, err, pad;
+  u32 n_touched, n_new_blocks, err;
+  u32 inv_first_new;  // ~(lowest pool index this frame allocated), 0 when it allocated none: what a dropped frame is rolled back to
   // one word takes ~88 atomics/us on this chip: the counters that every wave of a large grid adds to are sharded over 64
   // cache lines (index = workgroup id & 63) and summed by the host.  [s][0] valid points, [s][1] rays cast, [s][2] updates
   u32 shard[64][16];
@@ -125,10 +127,16 @@ __device__ __forceinline__ void block_dda_step(BlockDda& d) {
 // lane reads there -- old or new -- is a marked block; relaxed LDS accesses, no ordering needed.
 constexpr u32 kSeenSlots = 256;
 __global__ void __launch_bounds__(256) k_proj_points(ProjParams P, const float* __restrict__ xyz, u32* __restrict__ range, ProjLayer L, u32* __restrict__ touched_slots,
-                                                     ProjCounters* cnt, u32* layer_err) {
+                                                     ProjCounters* cnt, u32* layer_err, u32* stalled) {
   __shared__ u64 seen[kSeenSlots];
+  __shared__ u32 stall_seen;
   seen[threadIdx.x] = kEmptyKey;
+  if (threadIdx.x == 0) stall_seen = __hip_atomic_load(stalled, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
+  // A frame is all or nothing.  One that ran out of pool leaves its number in *stalled: the rest of it and every frame queued
+  // behind it do nothing (frames must reach the layer in call order) until the host has grown or repaired the layer and
+  // enqueued them again (proj_recover).  Whatever this frame marked before is undone by that repair.
+  if (stall_seen != 0u) return;
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   const u32 lane = lane_id();
   bool valid = false, casts = false;
@@ -185,9 +193,10 @@ __global__ void __launch_bounds__(256) k_proj_points(ProjParams P, const float* 
         L.ht_vals[slot] = pool;
         L.block_keys[pool] = bkey;
         atomicAdd(&cnt->n_new_blocks, 1u);
+        atomicMax(&cnt->inv_first_new, ~pool);
       } else {
         atomicSub(L.d_nblocks, 1u);
-        atomicOr(layer_err, kErrPool);
+        atomicCAS(stalled, 0u, P.seq);
       }
     }
     if (__hip_atomic_load(&L.ht_stamp[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != P.frame_id &&
@@ -226,8 +235,18 @@ __device__ __forceinline__ float proj_interpolate(const ProjParams& P, const u32
 // block left the chip empty and took 16 such chains per thread (33 us however few blocks); the block still streams through
 // registers, 48 KB read + 48 KB written, coalesced
 __global__ void __launch_bounds__(256) k_proj_update(ProjParams P, const u32* __restrict__ range, ProjLayer L, const u32* __restrict__ touched_slots, ProjCounters* cnt,
-                                                     u32* layer_err, u32* __restrict__ h_nblocks) {
+                                                     u32* layer_err, u32* __restrict__ h_nblocks, const u32* __restrict__ stalled, u32* __restrict__ h_stall) {
   constexpr u32 kParts = 8, kPartVoxels = kVoxelsPerBlock / kParts;
+  // k_proj_points of this frame is over: the stall word is the same for every thread of this grid
+  const u32 stall = *stalled;
+  if (stall != 0u) {  // no partial frame: nothing is applied
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      if (stall == P.seq) h_stall[1] = ~cnt->inv_first_new;  // the frame that ran out: the pool index its allocations start at (~0: none)
+      __threadfence_system();
+      h_stall[0] = stall;
+    }
+    return;
+  }
   const u32 n_touched = cnt->n_touched;
   u32 updates = 0;
   for (u32 t8 = blockIdx.x; t8 < n_touched * kParts; t8 += gridDim.x) {
@@ -298,6 +317,18 @@ struct cox_projective {
   hipEvent_t ring[4] = {};  // end of the last four frames: at most four are in flight (bounds how old the host's view of the pool is)
   uint64_t frames = 0;
   u64 blocks_seen = 0, blocks_delta_max = 0;
+  // Pool overflow (slow path).  d_stall: 0, or the number (ProjParams::seq) of the first frame that found no pool block; while it
+  // is set the device drops every frame whole.  h_stall (pinned): [0] its copy, left by the last kernel of every dropped frame,
+  // [1] the pool index that frame's own allocations start at.  The frames that may still be in flight are kept to be enqueued again.
+  u32* d_stall = nullptr;
+  u32* h_stall = nullptr;
+  struct Frame {
+    float T[7];
+    const float* xyz;
+    uint64_t n;
+    int deintegrate;
+  } inflight[4] = {};
+  int deferred = COX_OK;  // what settling on behalf of another writer ended with: reported by this integrator's next call
 };
 
 #define COX_TRY(expr)              \
@@ -310,9 +341,15 @@ void cox_proj_destroy(cox_projective* P) {
   if (!P) return;
   (void)hipSetDevice(P->layer->device);
   if (P->stream) (void)hipStreamSynchronize(P->stream);
-  for (void* q : {static_cast<void*>(P->range), static_cast<void*>(P->touched_slots), static_cast<void*>(P->cnt), static_cast<void*>(P->own_xyz)})
+  if (P->layer->settle_ctx == P) {
+    P->layer->settle_writer = nullptr;
+    P->layer->settle_ctx = nullptr;
+  }
+  for (void* q : {static_cast<void*>(P->range), static_cast<void*>(P->touched_slots), static_cast<void*>(P->cnt), static_cast<void*>(P->own_xyz),
+                  static_cast<void*>(P->d_stall)})
     if (q) (void)hipFree(q);
   if (P->h_cnt) (void)hipHostFree(P->h_cnt);
+  if (P->h_stall) (void)hipHostFree(P->h_stall);
   for (hipEvent_t e : P->ring)
     if (e) (void)hipEventDestroy(e);
   if (P->stream) (void)hipStreamDestroy(P->stream);
@@ -335,6 +372,10 @@ int cox_proj_create(cox_layer* layer, const cox_tsdf_config* cfg, cox_projective
   ok = ok && hipMalloc(reinterpret_cast<void**>(&P->cnt), sizeof(ProjCounters)) == hipSuccess;
   ok = ok && hipHostMalloc(reinterpret_cast<void**>(&P->h_cnt), sizeof(ProjCounters), hipHostMallocDefault) == hipSuccess;
   ok = ok && hipMalloc(reinterpret_cast<void**>(&P->touched_slots), sizeof(u32) * layer->ht_cap) == hipSuccess;
+  ok = ok && hipMalloc(reinterpret_cast<void**>(&P->d_stall), sizeof(u32)) == hipSuccess;
+  ok = ok && hipHostMalloc(reinterpret_cast<void**>(&P->h_stall), 2 * sizeof(u32), hipHostMallocDefault) == hipSuccess;
+  ok = ok && hipMemset(P->d_stall, 0, sizeof(u32)) == hipSuccess;
+  if (ok) P->h_stall[0] = P->h_stall[1] = 0;
   P->touched_cap = layer->ht_cap;
   if (!ok || hipDeviceSynchronize() != hipSuccess) {
     cox_proj_destroy(P);
@@ -344,8 +385,74 @@ int cox_proj_create(cox_layer* layer, const cox_tsdf_config* cfg, cox_projective
   return COX_OK;
 }
 
+static int proj_enqueue(cox_projective* P, const float T[7], const float* xyz_dev, uint64_t n, int deintegrate);
+// the number frame `frames` (counted from 0) leaves in the stall word: 1 .. 2^32 - 1, never the 0 that means "no stall"
+constexpr u64 kSeqPeriod = 0xFFFFFFFFull;
+static inline u32 proj_seq(u64 frames) { return static_cast<u32>(frames % kSeqPeriod) + 1u; }
+
+// Slow path: a frame found no free pool block.  The device has dropped it and every frame behind it whole (k_proj_points);
+// the stream is idle when this is called.  The layer goes back to what it was before that frame (its block count to the
+// first block the frame allocated; the hash table is rebuilt, which drops the keys that got no block), then
+//   auto-grow on:  the pool doubles and the dropped frames (at most the four that can be in flight) are enqueued again, in order;
+//                  their device buffers are the caller's until sync, so they are still there;
+//   auto-grow off: (or no memory for a larger pool) the frames stay dropped: COX_ERR_POOL_EXHAUSTED, the layer as before them.
+static int proj_recover(cox_projective* P) {
+  cox_layer* L = P->layer;
+  for (int round = 0; P->h_stall[0] != 0u; ++round) {
+    const u32 back = (proj_seq(P->frames) + kSeqPeriod - P->h_stall[0]) % kSeqPeriod;  // frames to redo, oldest first
+    if (back == 0 || back > 4 || round > 32) return COX_ERR_INTERNAL;
+    cox_drain_submitters();  // other integrators on this layer: nothing of theirs is in flight while the table is rebuilt
+    COX_HIP(hipDeviceSynchronize());
+    u32 nb = 0;
+    COX_HIP(hipMemcpy(&nb, L->d_nblocks, sizeof(u32), hipMemcpyDeviceToHost));
+    nb = std::min<u32>(std::min<u32>(nb, static_cast<u32>(L->capacity)), P->h_stall[1]);
+    COX_HIP(hipMemcpy(L->d_nblocks, &nb, sizeof(u32), hipMemcpyHostToDevice));
+    COX_HIP(hipMemset(P->d_stall, 0, sizeof(u32)));
+    P->h_stall[0] = 0u;
+    P->h_stall[1] = 0u;
+    int grown = COX_ERR_POOL_EXHAUSTED;
+    if (L->auto_grow && L->capacity < (1ull << 26)) {
+      grown = cox_internal_layer_reserve(L, std::min<u64>(2 * L->capacity, 1ull << 26));  // copies nb blocks, rebuilds the table
+      if (grown == COX_ERR_OUT_OF_MEMORY) L->auto_grow = false;
+      if (grown != COX_OK && grown != COX_ERR_OUT_OF_MEMORY) return grown;
+    }
+    if (grown != COX_OK) {
+      COX_TRY(cox_internal_layer_rebuild_table(L, nb));
+      P->pending = false;
+      P->last = cox_frame_stats{};
+      fprintf(stderr, "[coxgraph_hip] projective integrator: block pool exhausted (%llu blocks, auto-grow off or out of memory): %u frame(s) dropped whole\n",
+              static_cast<unsigned long long>(L->capacity), back);
+      return COX_ERR_POOL_EXHAUSTED;
+    }
+    cox_projective::Frame redo[4];
+    for (u32 k = 0; k < back; ++k) redo[k] = P->inflight[(P->frames - back + k) & 3];
+    P->frames -= back;
+    for (u32 k = 0; k < back; ++k) COX_TRY(proj_enqueue(P, redo[k].T, redo[k].xyz, redo[k].n, redo[k].deintegrate));
+    COX_HIP(hipStreamSynchronize(P->stream));
+  }
+  return COX_OK;
+}
+
+// Another integrator is about to write the layer (cox_layer_order_writer, on its caller's thread): every frame of this one is on
+// the layer, or dropped for good, before that.  Otherwise a frame dropped for want of pool would be redone behind the other
+// integrator's frame, and rolling it back would take that frame's blocks with it.  What goes wrong here is this integrator's to report.
+static void proj_settle(void* ctx) {
+  cox_projective* P = static_cast<cox_projective*>(ctx);
+  if (!P->pending && P->h_stall[0] == 0u) return;
+  int st = hipStreamSynchronize(P->stream) == hipSuccess ? COX_OK : COX_ERR_NO_DEVICE;
+  if (st == COX_OK && P->h_stall[0] != 0u) st = proj_recover(P);
+  if (st != COX_OK && P->deferred == COX_OK) P->deferred = st;
+}
+static inline int proj_take_deferred(cox_projective* P) {
+  const int st = P->deferred;
+  P->deferred = COX_OK;
+  return st;
+}
+
 static int proj_finish(cox_projective* P) {
+  COX_TRY(proj_take_deferred(P));
   COX_HIP(hipStreamSynchronize(P->stream));
+  if (P->h_stall[0] != 0u) COX_TRY(proj_recover(P));
   if (P->pending) {
     const ProjCounters& c = *P->h_cnt;
     u64 sums[3] = {0, 0, 0};
@@ -369,27 +476,13 @@ static int proj_finish(cox_projective* P) {
   return err_bits_to_status(lerr);
 }
 
-int cox_proj_integrate(cox_projective* P, const float T[7], const float* xyz_dev, uint64_t n, int deintegrate) {
+// one frame onto the stream (no host-side wait): the range image, the counters and the marked-block list are cleared / rewritten
+// by the frame itself
+static int proj_enqueue(cox_projective* P, const float T[7], const float* xyz_dev, uint64_t n, int deintegrate) {
   cox_layer* L = P->layer;
   hipStream_t s = P->stream;
-  // Frames queue up on ONE in-order stream: the range image, the counters and the marked-block list are cleared / rewritten
-  // by the frame itself, so a frame needs no host-side wait for its predecessor; statistics and errors are those of the last
-  // frame / sticky in the layer's error word and are read when somebody asks (sync, last_stats).
-  // Layer::allocateBlockPtrByIndex never fails upstream: double the pool once it is half full -- or will be, at the rate blocks
-  // have been allocated lately (the host's view of the count is up to four frames old)
-  if (P->frames >= 4) COX_HIP(hipEventSynchronize(P->ring[P->frames & 3]));  // frame t-4 is done
-  const u64 n_seen = *L->h_nblocks;
-  if (n_seen > P->blocks_seen) P->blocks_delta_max = std::max<u64>(P->blocks_delta_max, n_seen - P->blocks_seen);
-  P->blocks_seen = n_seen;
-  const u64 need = std::max<u64>(2 * n_seen, n_seen + 6 * P->blocks_delta_max);
-  if (L->auto_grow && need > L->capacity && L->capacity < (1ull << 26)) {
-    COX_HIP(hipStreamSynchronize(s));
-    u64 cap = L->capacity;
-    while (cap < need && cap < (1ull << 26)) cap *= 2;
-    const int st = cox_internal_layer_reserve(L, std::min<u64>(cap, 1ull << 26));
-    if (st != COX_OK && st != COX_ERR_OUT_OF_MEMORY) return st;
-    if (st == COX_ERR_OUT_OF_MEMORY) L->auto_grow = false;
-  }
+  // first: a projective integrator that wrote this layer last settles its frames in here, and may grow the layer doing so
+  const bool foreign_writer = cox_layer_order_writer(L, P);
   if (P->layer_generation != L->generation || P->touched_cap < L->ht_cap) {
     COX_HIP(hipStreamSynchronize(s));
     (void)hipFree(P->touched_slots);
@@ -398,10 +491,8 @@ int cox_proj_integrate(cox_projective* P, const float T[7], const float* xyz_dev
     P->touched_cap = L->ht_cap;
     P->layer_generation = L->generation;
   }
-  if (n == 0 && P->pending) COX_TRY(proj_finish(P));  // an empty frame enqueues nothing: settle the statistics of the one before it first
   P->last = cox_frame_stats{};
   P->last.n_points = n;
-  if (n == 0) return COX_OK;
   const cox_tsdf_config& c = P->cfg;
   ProjParams pp;
   memset(&pp, 0, sizeof(pp));
@@ -436,13 +527,21 @@ int cox_proj_integrate(cox_projective* P, const float T[7], const float* xyz_dev
   pp.deintegrate = deintegrate;
   pp.n_points = static_cast<u32>(n);
   pp.frame_id = ++L->frame_id;
+  pp.seq = proj_seq(P->frames);
+  cox_projective::Frame& fr = P->inflight[P->frames & 3];
+  memcpy(fr.T, T, sizeof(fr.T));
+  fr.xyz = xyz_dev;
+  fr.n = n;
+  fr.deintegrate = deintegrate;
   const ProjLayer PL{L->voxels, L->ht_keys, L->ht_vals, L->ht_stamp, L->block_keys, L->d_nblocks, L->ht_cap - 1, static_cast<u32>(L->capacity)};
   const size_t px = static_cast<size_t>(pp.rows) * pp.cols;
-  if (cox_layer_order_writer(L, P)) cox_layer_wait_writes(L, s);  // another integrator wrote this layer last
+  if (foreign_writer) cox_layer_wait_writes(L, s);  // another integrator wrote this layer last
+  L->settle_writer = proj_settle;
+  L->settle_ctx = P;
   COX_HIP(hipMemsetAsync(P->range, 0x7F, sizeof(u32) * px, s));
   COX_HIP(hipMemsetAsync(P->cnt, 0, sizeof(ProjCounters), s));
-  hipLaunchKernelGGL(k_proj_points, dim3(static_cast<u32>((n + 255) / 256)), dim3(256), 0, s, pp, xyz_dev, P->range, PL, P->touched_slots, P->cnt, L->d_err);
-  hipLaunchKernelGGL(k_proj_update, dim3(8192), dim3(256), 0, s, pp, P->range, PL, P->touched_slots, P->cnt, L->d_err, L->h_nblocks);
+  hipLaunchKernelGGL(k_proj_points, dim3(static_cast<u32>((n + 255) / 256)), dim3(256), 0, s, pp, xyz_dev, P->range, PL, P->touched_slots, P->cnt, L->d_err, P->d_stall);
+  hipLaunchKernelGGL(k_proj_update, dim3(8192), dim3(256), 0, s, pp, P->range, PL, P->touched_slots, P->cnt, L->d_err, L->h_nblocks, P->d_stall, P->h_stall);
   COX_HIP(hipMemcpyAsync(P->h_cnt, P->cnt, sizeof(ProjCounters), hipMemcpyDeviceToHost, s));
   COX_HIP(hipEventRecord(L->last_write, s));
   COX_HIP(hipEventRecord(P->ring[P->frames & 3], s));
@@ -451,6 +550,43 @@ int cox_proj_integrate(cox_projective* P, const float T[7], const float* xyz_dev
   P->pending = true;
   COX_HIP(hipGetLastError());
   return COX_OK;
+}
+
+// The device buffer of a frame is read asynchronously and must stay valid and unchanged until cox_integrator_sync / last_stats
+// (a frame that runs out of pool is read a second time, after the layer has grown).
+int cox_proj_integrate(cox_projective* P, const float T[7], const float* xyz_dev, uint64_t n, int deintegrate) {
+  cox_layer* L = P->layer;
+  hipStream_t s = P->stream;
+  // Frames queue up on ONE in-order stream and need no host-side wait for their predecessor; statistics and errors are those of
+  // the last frame / sticky in the layer's error word and are read when somebody asks (sync, last_stats).
+  // Layer::allocateBlockPtrByIndex never fails upstream: double the pool once it is half full -- or will be, at the rate blocks
+  // have been allocated lately (the host's view of the count is up to four frames old).  A frame that overflows all the same
+  // (the first frame of a small pool, a far wall appearing) is dropped whole by the device and redone by proj_recover.
+  COX_TRY(proj_take_deferred(P));
+  if (P->frames >= 4) COX_HIP(hipEventSynchronize(P->ring[P->frames & 3]));  // frame t-4 is done
+  if (P->h_stall[0] != 0u) {  // pinned word, no synchronisation on the fast path
+    COX_HIP(hipStreamSynchronize(s));
+    COX_TRY(proj_recover(P));
+  }
+  const u64 n_seen = *L->h_nblocks;
+  if (n_seen > P->blocks_seen) P->blocks_delta_max = std::max<u64>(P->blocks_delta_max, n_seen - P->blocks_seen);
+  P->blocks_seen = n_seen;
+  const u64 need = std::max<u64>(2 * n_seen, n_seen + 6 * P->blocks_delta_max);
+  if (L->auto_grow && need > L->capacity && L->capacity < (1ull << 26)) {
+    COX_HIP(hipStreamSynchronize(s));
+    if (P->h_stall[0] != 0u) COX_TRY(proj_recover(P));
+    u64 cap = L->capacity;
+    while (cap < need && cap < (1ull << 26)) cap *= 2;
+    const int st = cox_internal_layer_reserve(L, std::min<u64>(cap, 1ull << 26));
+    if (st != COX_OK && st != COX_ERR_OUT_OF_MEMORY) return st;
+    if (st == COX_ERR_OUT_OF_MEMORY) L->auto_grow = false;
+  }
+  if (n == 0) {
+    if (P->pending) COX_TRY(proj_finish(P));  // an empty frame enqueues nothing: settle the statistics of the one before it first
+    P->last = cox_frame_stats{};
+    return COX_OK;
+  }
+  return proj_enqueue(P, T, xyz_dev, n, deintegrate);
 }
 
 int cox_proj_integrate_host(cox_projective* P, const float T[7], const float* xyz, uint64_t n, int deintegrate) {

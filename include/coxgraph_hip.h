@@ -175,6 +175,10 @@ int cox_integrate_points_ex(cox_integrator_t* integ, const float T_G_C[7], const
  *      makes the engine wait for what that stream has enqueued so far, and makes that stream wait until the engine has read
  *      the inputs -- the call behaves as if the read happened on the caller's stream, so a stream-ordered allocator
  *      (e.g. PyTorch's, for tensors allocated on that stream) may recycle the buffers as soon as the caller drops them.
+ * The PROJECTIVE integrator supports (a) only: a frame that finds no free pool block is dropped whole on the device and read a
+ * second time, after the layer has grown, so xyz_dev stays the caller's, alive and unmodified, until cox_integrator_sync /
+ * cox_integrator_last_stats.  With auto-grow off such a frame, and those queued behind it, stay dropped: the call that notices (a
+ * later integrate call, which then enqueues nothing, or the sync) returns COX_ERR_POOL_EXHAUSTED and the layer is as before them.
  * Readers of the layer (cox_reg_*, cox_regpoints_from_layer, downloads, clones) wait for the frames in flight by themselves. */
 int cox_integrate_points_dev(cox_integrator_t* integ, const float T_G_C[7], const float* xyz_dev, const uint8_t* rgba_dev, uint64_t n, int freespace);
 /* TsdfIntegratorBase::integratePointCloud(T_G_C, points_C, colors, freespace_points) as the reference calls it -- with HOST

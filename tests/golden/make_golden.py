@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Regenerates tests/golden/oracle_golden.npz from the CPU oracle.
+"""Regenerates tests/golden/oracle_golden.npz -- or, with the argument `projective`, tests/golden/projective_golden.npz
+(the cases of tests/test_golden_projective.py) -- from the CPU oracle.
 
 The reference (mfkiwl/coxgraph) holds NO golden vectors for this path (it has no tests at all and its hot-path
 arithmetic lives in un-vendored forks), so these fixtures are NOT reference outputs: they freeze the behaviour of
@@ -7,7 +8,7 @@ this repository's own oracle (parity unpinned, see oracle/cox_oracle.hpp) so tha
 oracle shows up in the CPU suite and (b) the GPU suite has a second, oracle-independent-at-run-time target.
 Inputs are small and synthetic; every array is data (inputs + expected outputs), no code.
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [projective]
 """
 import ctypes as C
 import hashlib
@@ -106,6 +107,10 @@ def build(eng):
 
 if __name__ == "__main__":
     eng = Engine(os.path.join(ROOT, "oracle", "libcoxoracle.so"), "coxo_")
-    out = os.path.join(ROOT, "tests", "golden", "oracle_golden.npz")
-    np.savez_compressed(out, **build(eng))
+    if sys.argv[1:] == ["projective"]:
+        from test_golden_projective import build_golden, PATH as out  # noqa: E402
+        np.savez_compressed(out, **build_golden(eng))
+    else:
+        out = os.path.join(ROOT, "tests", "golden", "oracle_golden.npz")
+        np.savez_compressed(out, **build(eng))
     print("wrote", out, os.path.getsize(out), "bytes")
