@@ -1,0 +1,495 @@
+// Ray generation (stages H, P, M): one ray per point (simple), or points bundled by terminal voxel and merged by the sequential
+// weighted mean (merged: frame hash, sort keys, bundle boundaries, merge) -- part of cox_integrator.hip (included there, in this
+// order: the kernels use what is defined above them in that file).
+#pragma once
+
+// ---- simple: one ray per point, ray id = mixed-order sequence number --------------------------
+__global__ void __launch_bounds__(256) k_rays_simple(const FrameParams* __restrict__ Pp, RayArrays R,
+                                                     Counters* cnt) {
+  const FrameParams P = *Pp;
+  const u32 seq = blockIdx.x * blockDim.x + threadIdx.x;
+  if (seq == 0) cnt->n_ray_slots = P.n_points;
+  if (seq >= P.n_points) return;
+  const u32 idx = mixed_index(seq, P.n_points);
+  const F3 p{P.xyz[3 * idx], P.xyz[3 * idx + 1], P.xyz[3 * idx + 2]};
+  bool clearing = false;
+  const bool valid = point_valid(P, p, &clearing);
+  u32 nsteps = 0, flags = 0;
+  if (valid) {
+    const F3 pg = transform_point(P, p);
+    Dda d;
+    dda_setup(d, P, pg, clearing);
+    if (d.range_error) atomicOr(&cnt->err, kErrRange);
+    nsteps = d.nsteps;
+    flags = 1u | (clearing ? 2u : 0u);
+    R.px[seq] = pg.x;
+    R.py[seq] = pg.y;
+    R.pz[seq] = pg.z;
+    R.w[seq] = voxel_weight(P, p);
+    R.color[seq] = pack_rgba_wire(P.rgba, idx);
+  }
+  R.flags[seq] = flags;
+  R.nsteps[seq] = nsteps;
+  const u64 m = __ballot(valid);
+  if (lane_id() == 0 && m) {
+    u32* sh = cnt->shard[(seq >> 6) & 63u];
+    atomicAdd(&sh[kShValid], static_cast<u32>(__popcll(m)));
+    atomicAdd(&sh[kShRays], static_cast<u32>(__popcll(m)));
+  }
+}
+
+// ---- merged: bundle points by terminal voxel ---------------------------------------------------
+// thread = point (so neighbouring lanes are neighbouring pixels and mostly share a terminal voxel): the lanes of a
+// wave that hold the same key elect one leader, which inserts the key in the per-frame hash once and records the
+// smallest sequence number of the group as a candidate for the bundle's first visit.
+// First kernel of a frame: with by_value the frame's parameter block arrives as a kernel argument and workgroup 0
+// stores it for the kernels that follow (saves the 4 us H2D blit per frame); captured stage graphs keep the copy.
+// n_dev (by_value only): the frame's point count is still on the device (depth front end): every workgroup takes it from there.
+__device__ __forceinline__ u32 pow2_above(u32 n) {  // power of two > n (FrameParams::np2)
+  u32 p = 1;
+  while (p <= n && p < 0x80000000u) p <<= 1;
+  return p;
+}
+__global__ void __launch_bounds__(256) k_bundle_insert(FrameParams* __restrict__ Pp, FrameParams Pv, int by_value, const u32* __restrict__ n_dev, u64* __restrict__ fh_keys,
+                                                       u32* __restrict__ fh_first, u32 fh_mask, u32* __restrict__ pslot, Counters* cnt) {
+  // (the count is taken into a scalar of its own: writing it into the by-value parameter struct sends the whole struct through
+  // scratch memory -- 42 MB of writes and 11 us per launch, seen in the PMC pass)
+  const FrameParams P = by_value ? Pv : *Pp;
+  const u32 n_points = (by_value && n_dev) ? min(*n_dev, P.n_points) : P.n_points;
+  if (by_value && blockIdx.x == 0 && threadIdx.x == 0) {
+    *Pp = Pv;
+    if (n_dev) {
+      Pp->n_points = n_points;
+      Pp->np2 = pow2_above(n_points);
+    }
+  }
+  const u32 idx = blockIdx.x * blockDim.x + threadIdx.x;
+  const u32 lane = lane_id();
+  bool valid = false;
+  u64 key = 0;
+  u32 seq = kInvalid;
+  if (idx < n_points) {
+    seq = mixed_sequence(idx, n_points);
+    const F3 p{P.xyz[3 * idx], P.xyz[3 * idx + 1], P.xyz[3 * idx + 2]};
+    bool clearing = false;
+    valid = point_valid(P, p, &clearing);
+    if (valid) {
+      const F3 pg = transform_point(P, p);
+      const float sx = pg.x * P.voxel_size_inv, sy = pg.y * P.voxel_size_inv, sz = pg.z * P.voxel_size_inv;
+      if (!(index_in_range(sx) && index_in_range(sy) && index_in_range(sz))) {  // also catches NaN
+        atomicOr(&cnt->err, kErrRange);
+        valid = false;
+      } else {
+        key = pack_key(grid_index(sx), grid_index(sy), grid_index(sz)) | (clearing ? (1ull << 63) : 0ull);
+      }
+    }
+  }
+  // group the lanes by key (ALU only), then let all group leaders touch memory at the same time
+  u32 my_leader = lane, group_min = kInvalid;
+  bool is_leader = false;
+  u64 todo = __ballot(valid);
+  while (todo) {
+    const u32 leader = static_cast<u32>(__ffsll(static_cast<long long>(todo))) - 1u;
+    const u64 k = (static_cast<u64>(static_cast<u32>(__builtin_amdgcn_readlane(static_cast<u32>(key >> 32), leader))) << 32) |
+                  static_cast<u64>(static_cast<u32>(__builtin_amdgcn_readlane(static_cast<u32>(key), leader)));
+    const bool mine = valid && key == k;
+    const u64 peers = __ballot(mine);
+    u32 mn = mine ? seq : kInvalid;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mn = min(mn, static_cast<u32>(__shfl_xor(static_cast<int>(mn), off, 64)));
+    if (mine) my_leader = leader;
+    if (lane == leader) {
+      is_leader = true;
+      group_min = mn;
+    }
+    todo &= ~peers;
+  }
+  u32 sl = kInvalid;
+  if (is_leader) {
+    bool fresh;
+    sl = ht_insert(fh_keys, fh_mask, key, &fresh);
+    if (sl == kInvalid)
+      atomicOr(&cnt->err, kErrTable);
+    else if (__hip_atomic_load(&fh_first[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > group_min)
+      atomicMin(&fh_first[sl], group_min);  // a stale (larger) value read above only costs this atomic
+  }
+  const u32 got = static_cast<u32>(__shfl(static_cast<int>(sl), static_cast<int>(my_leader), 64));
+  const u32 slot = valid ? got : kInvalid;
+  if (idx < n_points) pslot[idx] = slot;  // kInvalid for points that are not integrated; indexed by point (coalesced)
+  const u64 m = __ballot(valid && slot != kInvalid);
+  if (lane == 0 && m) atomicAdd(&cnt->shard[(idx >> 6) & 63u][kShValid], static_cast<u32>(__popcll(m)));
+}
+// the same for the frames whose parameter block is uploaded by a copy (simple, fast, captured stage graphs): one thread patches it
+__global__ void k_params_count(FrameParams* __restrict__ Pp, const u32* __restrict__ n_dev) {
+  const u32 n = min(*n_dev, Pp->n_points);
+  Pp->n_points = n;
+  Pp->np2 = pow2_above(n);
+}
+// sort key of a point = (clearing ? np2 : 0) + first sequence number of its bundle; value = seq.  Also publishes the
+// key width of the bundling sort.
+__global__ void __launch_bounds__(256) k_bundle_keys(const FrameParams* __restrict__ Pp, const u64* __restrict__ fh_keys, const u32* __restrict__ fh_first,
+                                                     const u32* __restrict__ pslot, u32* __restrict__ skey, u32* __restrict__ sval, SortInfo* sort_info) {
+  const u32 n = Pp->n_points, np2 = Pp->np2;
+  const u32 seq = blockIdx.x * blockDim.x + threadIdx.x;
+  if (seq == 0) {
+    u32 bits = 1;  // clearing bit + log2(np2); kInvalid's low bits exceed every valid key
+    while ((1u << (bits - 1)) < np2) ++bits;
+    sort_info->nbits = bits;
+    sort_info->parity = 0;
+    sort_info->base = 0;
+  }
+  if (seq >= n) return;
+  const u32 slot = pslot[mixed_index(seq, n)];  // the bundling sort starts from visiting order: gather on the read side
+  u32 k = kInvalid;
+  if (slot != kInvalid) k = fh_first[slot] + ((fh_keys[slot] >> 63) ? np2 : 0u);
+  skey[seq] = k;
+  sval[seq] = seq;
+}
+// the two ping-pong buffers of the bundling sort + where its result ended up
+struct BundleView {
+  const u32* key[2];
+  const u32* val[2];
+  const SortInfo* info;
+};
+// Bundle boundaries in two launches (round 1 used five: head flags, a three-kernel scan, starts).  A head is a sorted position
+// whose key differs from its predecessor's; a bundle's ordinal is the number of heads before it.
+//   k_bundle_count   per tile of 2048 positions: number of heads
+//   k_bundle_starts  per tile: its base = sum of the counts of the tiles before it (every workgroup adds them up itself --
+//                    a frame has ~150 tiles; a ticketed "last workgroup scans" tail took 12 us, this takes none), heads
+//                    again, in-tile exclusive scan, bstart[base + rank] = position; the last tile publishes the bundle count
+constexpr u32 kBoundTile = 2048;
+__device__ __forceinline__ bool bundle_head(const u32* __restrict__ skey, u32 i, u32 n) {
+  if (i >= n) return false;
+  const u32 k = skey[i];
+  return k != kInvalid && (i == 0 || skey[i - 1] != k);
+}
+// The frame hash is sized for "every point its own bundle" (6 MB) but a frame fills a few thousand slots: instead of a memset
+// per frame, the slots the frame used are put back to empty once its keys have been read (duplicates write the same words) --
+// here, behind the bundling sort (round 2 had a launch of its own for it right behind k_bundle_keys).
+__global__ void __launch_bounds__(256) k_bundle_count(const FrameParams* __restrict__ Pp, BundleView V, u32* __restrict__ tile_sums, const u32* __restrict__ pslot,
+                                                      u64* __restrict__ fh_keys, u32* __restrict__ fh_first, int self_clean) {
+  __shared__ u32 lds[4];
+  const u32 n = Pp->n_points;
+  const u32* __restrict__ skey = V.key[V.info->parity & 1u];
+  const u32 n_tiles = (n + kBoundTile - 1) / kBoundTile;
+  for (u32 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    u32 c = 0;
+#pragma unroll
+    for (u32 q = 0; q < kBoundTile / 256; ++q) {
+      const u32 i = tile * kBoundTile + q * 256 + threadIdx.x;
+      c += bundle_head(skey, i, n) ? 1u : 0u;
+      if (self_clean && i < n) {
+        const u32 slot = pslot[i];
+        if (slot != kInvalid) {
+          fh_keys[slot] = kEmptyKey;
+          fh_first[slot] = 0xFFFFFFFFu;
+        }
+      }
+    }
+    u32 tot;
+    (void)block_exclusive_scan<4>(c, &tot, lds);
+    if (threadIdx.x == 0) tile_sums[tile] = tot;
+  }
+}
+__global__ void __launch_bounds__(256) k_bundle_starts(const FrameParams* __restrict__ Pp, BundleView V, const u32* __restrict__ tile_sums, u32* __restrict__ bstart,
+                                                       Counters* cnt) {
+  __shared__ u32 lds[4], lds2[4];
+  const u32 n = Pp->n_points;
+  const u32* __restrict__ skey = V.key[V.info->parity & 1u];
+  const u32 n_tiles = (n + kBoundTile - 1) / kBoundTile;
+  if (n_tiles == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+    cnt->n_rays = 0;
+    cnt->n_ray_slots = 0;
+  }
+  for (u32 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    u32 below = 0;
+    for (u32 t = threadIdx.x; t < tile; t += 256) below += tile_sums[t];
+    u32 base;
+    (void)block_exclusive_scan<4>(below, &base, lds2);
+    // thread t owns the 8 consecutive positions [tile * 2048 + 8 t, + 8)
+    const u32 i0 = tile * kBoundTile + threadIdx.x * 8;
+    bool h[8];
+    u32 c = 0;
+#pragma unroll
+    for (u32 q = 0; q < 8; ++q) {
+      h[q] = bundle_head(skey, i0 + q, n);
+      c += h[q] ? 1u : 0u;
+    }
+    u32 tot;
+    u32 rank = base + block_exclusive_scan<4>(c, &tot, lds);
+#pragma unroll
+    for (u32 q = 0; q < 8; ++q) {
+      const u32 i = i0 + q;
+      if (h[q]) bstart[rank++] = i;
+      if (i < n && skey[i] != kInvalid && (i + 1 == n || skey[i + 1] == kInvalid)) cnt->n_sorted_valid = i + 1;  // invalid keys sort last: one writer
+    }
+    if (tile + 1 == n_tiles && threadIdx.x == 0) {
+      cnt->n_rays = base + tot;  // number of bundles
+      cnt->n_ray_slots = base + tot;
+    }
+  }
+}
+
+// two waves per bundle: the sequential weighted mean of its points in visiting order, bit-exact with the
+// single-threaded reference loop
+//     merged = (merged * W + p * w) / (W + w);  colour = blend(colour, W, c, w);  W += w
+// Each component is a recurrence  val <- f_k(val)  whose operands do not depend on the running value:
+//     x, y, z (wave 0):     val <- (val * W_k + p * w) / (W_k + w)                   one IEEE divide per step
+//     a, b, g, r (wave 1):  val <- round(val * (W_k/(W_k+w)) + c * (w/(W_k+w)))      multiply-add-round per step
+// 64 points at a time are gathered in parallel and their operands are computed lane-parallel into an LDS table
+// [point][component]; lanes 0-3 then carry one component each through the dependent chain with one (prefetched)
+// LDS read per step and no branches.  The chain length is the bundle size, so the two chains of a big bundle run
+// side by side on different SIMDs instead of back to back.  Skipped points (w < eps, or anything after the first
+// point of a clearing bundle) are the identity step: (M, A, D) = (1, 0, 1).
+typedef float MergeOp __attribute__((ext_vector_type(4)));  // (M, A, D, 1/D)
+
+// Piece path (k_touch_pieces): a PIECE is a maximal run of consecutive steps of one ray inside one tile (block, z slab:
+// 16 x 16 x 1 voxels) -- the voxel coordinates of a walk are monotone, so a ray meets a tile in one run of at most 31
+// steps.  Pieces are written at fixed slots (exclusive scan of this bound over the rays), which keeps them in ray order
+// without a sort key for it.  The wave walk starts a piece at every round of 64 steps, at every z step and at every
+// change of the x / y block; its per-axis step counts are at most n_axis + 1 (wave_ray_path generates n_axis + 2 crossing
+// times and rejects a walk that uses the last one).  Rays that are known here to take the sequential walk get the
+// trivial bound (one piece per step); the + 4 covers a ray whose walk is only found to need the fallback later (and the
+// sequential walk makes no round pieces) -- if even that is exceeded the frame is dropped and reported, never wrong.
+__device__ __forceinline__ u32 piece_bound(const Dda& d, u32 axis_cap) {
+  const u32 ns = d.nsteps;
+  if (ns == 0) return 0;
+  const u32 gen = ns + 1;
+  const u32 g0 = min(d.n_axis[0] + 2, gen), g1 = min(d.n_axis[1] + 2, gen), g2 = min(d.n_axis[2] + 2, gen);
+  if (d.sgn[0] == 0 || d.sgn[1] == 0 || d.sgn[2] == 0 || g0 > axis_cap || g1 > axis_cap || g2 > axis_cap || ns > 3 * axis_cap) return ns;
+  const u32 b = (ns + 63) / 64 + (d.n_axis[2] + 1) + ((d.n_axis[0] + 1) / 16 + 1) + ((d.n_axis[1] + 1) / 16 + 1) + 4;
+  return min(b, ns);
+}
+
+__global__ void __launch_bounds__(256) k_bundle_merge(const FrameParams* __restrict__ Pp, BundleView V, const u32* __restrict__ bstart, RayArrays R, Counters* cnt,
+                                                      u32 piece_axis_cap) {
+  const FrameParams P = *Pp;
+  const u32 np2 = P.np2;
+  const float* __restrict__ xyz = P.xyz;
+  const uint8_t* __restrict__ rgba = P.rgba;
+  const u32 spar = uniform_u32(V.info->parity & 1u);
+  const u32* __restrict__ skey = V.key[spar];
+  const u32* __restrict__ sval = V.val[spar];
+  __shared__ MergeOp ops[4][64][4];
+  const u32 n_bundles = uniform_u32(cnt->n_rays);
+  const u32 n_valid = uniform_u32(cnt->n_sorted_valid);
+  const u32 tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const u32 nthreads = gridDim.x * blockDim.x;
+  const u32 lane = lane_id();
+  const u32 role = lane & 3u;
+  MergeOp(*tbl)[4] = ops[threadIdx.x >> 6];
+  for (u32 task = uniform_u32(tid >> 6); task < 2 * n_bundles; task += nthreads >> 6) {
+    const u32 m = task >> 1;
+    const bool colour_wave = (task & 1u) != 0;
+    const u32 begin = uniform_u32(bstart[m]);
+    const u32 end = uniform_u32((m + 1 < n_bundles) ? bstart[m + 1] : n_valid);
+    const bool clearing = uniform_u32(skey[begin]) >= np2;
+    if (!colour_wave && lane == 0) atomicMax(&cnt->shard[m & 63u][kShMaxBundle], end - begin);
+    if (colour_wave && rgba == nullptr) {  // no colours: Color() stays (0,0,0,0)
+      if (lane == 0) {
+        R.color[m] = 0u;
+        reinterpret_cast<u32*>(R.q)[static_cast<size_t>(m) * 8u + 5u] = 0u;
+      }
+      continue;
+    }
+    float val = 0.0f;  // this lane's component of the running mean / colour channel
+    float W = 0.0f;    // uniform
+    u64 key = 0;
+    bool done = false;
+    for (u32 base = begin; base < end && !done; base += 64) {
+      const u32 i = base + lane;
+      const u32 cnt_in = min(64u, end - base);
+      float px = 0.0f, py = 0.0f, pz = 0.0f, w = 0.0f;
+      u32 col = 0;
+      if (i < end) {
+        const u32 idx = mixed_index(sval[i], P.n_points);
+        px = xyz[3 * idx];
+        py = xyz[3 * idx + 1];
+        pz = xyz[3 * idx + 2];
+        w = voxel_weight(P, F3{px, py, pz});
+        if (colour_wave) col = pack_rgba_wire(rgba, idx);
+      }
+      if (base == begin && !colour_wave) {
+        const F3 pg = transform_point(P, F3{readlane_f32(px, 0), readlane_f32(py, 0), readlane_f32(pz, 0)});
+        key = pack_key(grid_index(pg.x * P.voxel_size_inv), grid_index(pg.y * P.voxel_size_inv), grid_index(pg.z * P.voxel_size_inv));
+      }
+      // which points take part
+      bool used = (lane < cnt_in) && !(w < kEps);
+      if (clearing) {  // only the first point of a clearing bundle is used
+        const u64 um = __ballot(used);
+        used = used && (lane == static_cast<u32>(__ffsll(static_cast<long long>(um))) - 1u);
+        if (um) done = true;
+      }
+      // W before each point of the chunk (skipped points leave W unchanged)
+      float Wpre;
+      const u64 in_mask = (cnt_in == 64) ? ~0ull : ((1ull << cnt_in) - 1ull);
+      if (!clearing && (__ballot(w == 1.0f) & in_mask) == in_mask && W == truncf(W) && W < 8388608.0f) {
+        Wpre = W + static_cast<float>(lane);  // integers: every partial sum is exact
+      } else {
+        float run = W;
+        Wpre = W;
+        const u64 used_mask = __ballot(used);
+        for (u32 k = 0; k < cnt_in; ++k) {
+          if (lane == k) Wpre = run;
+          const float wk = readlane_f32(w, k);
+          if ((used_mask >> k) & 1ull) run += wk;
+        }
+      }
+      const float den = Wpre + w;
+      const float Wnext = used ? den : Wpre;
+      const bool d_ok = !used || (den >= 9.094947e-13f && den <= 1.0995116e12f);  // divisor range of the fast division
+      // operand table of this chunk; rows beyond the chunk are the identity so the chain can run in groups of 4
+      {
+        MergeOp* row = tbl[lane];
+        const MergeOp ident{1.0f, 0.0f, 1.0f, 1.0f};
+        if (!used) {
+#pragma unroll
+          for (u32 c = 0; c < 4; ++c) row[c] = ident;
+        } else if (!colour_wave) {
+          const float r0 = __builtin_amdgcn_rcpf(den);
+          const float r = __builtin_fmaf(__builtin_fmaf(-den, r0, 1.0f), r0, r0);  // one Newton step: < 1 ulp from 1/den
+          row[0] = MergeOp{Wpre, px * w, den, r};
+          row[1] = MergeOp{Wpre, py * w, den, r};
+          row[2] = MergeOp{Wpre, pz * w, den, r};
+          row[3] = ident;
+        } else {
+          const float fa = Wpre / den, fb = w / den;  // colour blend factors of this point
+#pragma unroll
+          for (u32 c = 0; c < 4; ++c) row[c] = MergeOp{fa, static_cast<float>(static_cast<int>((col >> (8u * c)) & 255u)) * fb, 1.0f, 0.0f};
+        }
+      }
+      wave_lds_handover();
+      // the dependent chain
+      MergeOp nxt = tbl[0][role];
+      if (!colour_wave) {
+        // IEEE division with everything that depends only on the divisor hoisted off the chain: r = refined 1/D sits in
+        // the table; q0 = N r, then two residual corrections -- the same Newton sequence the compiler emits for '/',
+        // minus its range scaling.  A correctly rounded quotient is unique, so the bits equal the oracle's '/' whenever
+        // no intermediate can leave the normal range; |N| and |D| are tracked off the critical path and the chunk is
+        // redone with plain '/' if they ever left [2^-40, 2^40] (or N was 0, where the sign of zero would differ).
+        const float val_in = val;
+        float n_lo = 1.0f, n_hi = 1.0f;
+        // groups of 4 steps with the next group's operands already in flight: the LDS latency (~100 cycles) would
+        // otherwise bound every step of the chain
+        // Two register sets in turn (eight steps per round): the operands of one group of four are read from LDS while the other
+        // group's steps run, with scheduling barriers so that the reads are issued where they are written -- left alone, the compiler
+        // moves each group's first read to the top of its own steps and waits for it there (~100 cycles per four steps on the chain).
+        // Rows beyond the chunk are the identity, so a trailing group of four is harmless.
+        MergeOp a0 = tbl[0][role], a1 = tbl[1][role], a2 = tbl[2][role], a3 = tbl[3][role];
+        // (Going on with q1 and checking off the chain that the second correction would not have changed it does not pay: one step
+        // in a hundred needs that correction, so nearly every chunk of 3 x 64 steps had to be redone.)
+#define COX_MERGE_STEP(op)                                  \
+  {                                                         \
+    const float N = val * (op).x + (op).y;                  \
+    n_lo = fminf(n_lo, fabsf(N));                           \
+    n_hi = fmaxf(n_hi, fabsf(N));                           \
+    const float q0 = N * (op).w;                            \
+    const float e0 = __builtin_fmaf(-(op).z, q0, N);        \
+    const float q1 = __builtin_fmaf(e0, (op).w, q0);        \
+    const float e1 = __builtin_fmaf(-(op).z, q1, N);        \
+    val = __builtin_fmaf(e1, (op).w, q1);                   \
+  }
+        for (u32 k = 0; k < cnt_in; k += 8) {
+          const u32 kb = (k + 4) & 63u;
+          const MergeOp b0 = tbl[kb][role], b1 = tbl[kb + 1][role], b2 = tbl[kb + 2][role], b3 = tbl[kb + 3][role];
+          __builtin_amdgcn_sched_barrier(0);
+          COX_MERGE_STEP(a0)
+          COX_MERGE_STEP(a1)
+          COX_MERGE_STEP(a2)
+          COX_MERGE_STEP(a3)
+          __builtin_amdgcn_sched_barrier(0);
+          const u32 ka = (k + 8) & 63u;
+          a0 = tbl[ka][role];
+          a1 = tbl[ka + 1][role];
+          a2 = tbl[ka + 2][role];
+          a3 = tbl[ka + 3][role];
+          __builtin_amdgcn_sched_barrier(0);
+          COX_MERGE_STEP(b0)
+          COX_MERGE_STEP(b1)
+          COX_MERGE_STEP(b2)
+          COX_MERGE_STEP(b3)
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#undef COX_MERGE_STEP
+        const bool bad = (lane < 3) && !(n_lo >= 9.094947e-13f && n_hi <= 1.0995116e12f);  // NaN fails too
+        if (__ballot(bad || !d_ok)) {
+          val = val_in;
+          nxt = tbl[0][role];
+          for (u32 k = 0; k < cnt_in; ++k) {
+            const MergeOp op = nxt;
+            nxt = tbl[(k + 1) & 63u][role];
+            val = (val * op.x + op.y) / op.z;
+          }
+        }
+      } else {
+        // (the same two register sets in turn; the identity rows leave an integer as it is)
+        // roundf(x) for x >= 0 (a blend of non-negative values with non-negative factors): trunc(x), plus one where the -- exactly
+        // computed -- fraction reaches a half; two dependent operations fewer than the sign-preserving general form.
+#define COX_COLOUR_STEP(op)                                 \
+  {                                                         \
+    const float x = val * (op).x + (op).y;                  \
+    const float t = truncf(x);                              \
+    val = (x - t >= 0.5f) ? t + 1.0f : t;                   \
+  }
+        MergeOp a0 = tbl[0][role], a1 = tbl[1][role], a2 = tbl[2][role], a3 = tbl[3][role];
+        for (u32 k = 0; k < cnt_in; k += 8) {
+          const u32 kb = (k + 4) & 63u;
+          const MergeOp b0 = tbl[kb][role], b1 = tbl[kb + 1][role], b2 = tbl[kb + 2][role], b3 = tbl[kb + 3][role];
+          __builtin_amdgcn_sched_barrier(0);
+          COX_COLOUR_STEP(a0)
+          COX_COLOUR_STEP(a1)
+          COX_COLOUR_STEP(a2)
+          COX_COLOUR_STEP(a3)
+          __builtin_amdgcn_sched_barrier(0);
+          const u32 ka = (k + 8) & 63u;
+          a0 = tbl[ka][role];
+          a1 = tbl[ka + 1][role];
+          a2 = tbl[ka + 2][role];
+          a3 = tbl[ka + 3][role];
+          __builtin_amdgcn_sched_barrier(0);
+          COX_COLOUR_STEP(b0)
+          COX_COLOUR_STEP(b1)
+          COX_COLOUR_STEP(b2)
+          COX_COLOUR_STEP(b3)
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#undef COX_COLOUR_STEP
+      }
+      wave_lds_handover();
+      W = readlane_f32(Wnext, cnt_in - 1);
+    }
+    if (colour_wave) {
+      u32 mcolor = 0;
+#pragma unroll
+      for (u32 c = 0; c < 4; ++c) mcolor |= (static_cast<u32>(static_cast<int>(readlane_f32(val, c))) & 255u) << (8u * c);
+      if (lane == 0) {
+        R.color[m] = mcolor;
+        reinterpret_cast<u32*>(R.q)[static_cast<size_t>(m) * 8u + 5u] = mcolor;  // (the ray's line: the wave apply takes the colour from there)
+      }
+    } else {
+      const float mx = readlane_f32(val, 0), my = readlane_f32(val, 1), mz = readlane_f32(val, 2);
+      if (lane == 0) {
+        const F3 pg = transform_point(P, F3{mx, my, mz});
+        Dda d;
+        dda_setup(d, P, pg, clearing);
+        if (d.range_error) atomicOr(&cnt->err, kErrRange);
+        R.px[m] = pg.x;
+        R.py[m] = pg.y;
+        R.pz[m] = pg.z;
+        R.w[m] = W;
+        R.flags[m] = 1u | (clearing ? 2u : 0u);
+        R.key[m] = key;
+        R.nsteps[m] = d.nsteps;
+        if (piece_axis_cap) R.pbound[m] = piece_bound(d, piece_axis_cap);
+        {
+          // what compute_sdf derives from the ray alone, with its own operations, once per ray instead of once per step
+          const F3 dv = pg - F3{P.tx, P.ty, P.tz};
+          typedef float F4 __attribute__((ext_vector_type(4)));
+          F4* q = reinterpret_cast<F4*>(R.q + static_cast<size_t>(m) * 8u);
+          q[0] = F4{dv.x, dv.y, dv.z, sqrtf(dot3(dv, dv))};
+          R.q[static_cast<size_t>(m) * 8u + 4u] = W;  // (word 5 is the colour, written by the bundle's colour wave)
+        }
+      }
+    }
+  }
+}
