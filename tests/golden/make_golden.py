@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Regenerates tests/golden/oracle_golden.npz -- or, with the argument `projective`, tests/golden/projective_golden.npz
-(the cases of tests/test_golden_projective.py) -- from the CPU oracle.
+(the cases of tests/test_golden_projective.py), or, with `submap`, tests/golden/submap_golden.npz (the cases of
+tests/test_golden_submap.py) -- from the CPU oracle.
 
 The reference (mfkiwl/coxgraph) holds NO golden vectors for this path (it has no tests at all and its hot-path
 arithmetic lives in un-vendored forks), so these fixtures are NOT reference outputs: they freeze the behaviour of
@@ -8,7 +9,7 @@ this repository's own oracle (parity unpinned, see oracle/cox_oracle.hpp) so tha
 oracle shows up in the CPU suite and (b) the GPU suite has a second, oracle-independent-at-run-time target.
 Inputs are small and synthetic; every array is data (inputs + expected outputs), no code.
 
-    python tests/golden/make_golden.py [projective]
+    python tests/golden/make_golden.py [projective | submap]
 """
 import ctypes as C
 import hashlib
@@ -109,6 +110,9 @@ if __name__ == "__main__":
     eng = Engine(os.path.join(ROOT, "oracle", "libcoxoracle.so"), "coxo_")
     if sys.argv[1:] == ["projective"]:
         from test_golden_projective import build_golden, PATH as out  # noqa: E402
+        np.savez_compressed(out, **build_golden(eng))
+    elif sys.argv[1:] == ["submap"]:
+        from test_golden_submap import build_golden, PATH as out  # noqa: E402
         np.savez_compressed(out, **build_golden(eng))
     else:
         out = os.path.join(ROOT, "tests", "golden", "oracle_golden.npz")
