@@ -327,6 +327,12 @@ class Integrator:
         """Order *_dev calls against the caller's HIP stream (e.g. torch.cuda.current_stream().cuda_stream)."""
         self.eng.check(self.eng.fn("integrator_set_input_stream")(self.h, C.c_void_p(stream_ptr or 0), C.c_int(int(enable))), "integrator_set_input_stream")
 
+    def attach_history(self, obs):
+        """cox_integrator_attach_history: every cloud fused from now on is also recorded in `obs` (an ObservationHistory) under
+        its current frame id; None detaches."""
+        self.eng.check(self.eng.fn("integrator_attach_history")(self.h, obs.h if obs is not None else None), "integrator_attach_history")
+        self.history = obs  # (keeps the record alive while it is attached)
+
     def sync(self):
         self.eng.check(self.eng.fn("integrator_sync")(self.h), "integrator_sync")
 
@@ -378,6 +384,84 @@ class Integrator:
         self.eng.check(self.eng.fn("integrator_kernel_time")(self.h, C.byref(ms), C.byref(n), C.c_int(int(reset))),
                        "integrator_kernel_time")
         return float(ms.value), int(n.value)
+
+
+class ObservationHistory:
+    """Which frames saw which part of a submap (cox_obs_t, include/coxgraph_hip_history.h): per 16^3 block 64 cells of 4x4x4
+    voxels, per cell a 256-bit mask of frame ids."""
+    CELLS, WORDS = 64, 8
+
+    def __init__(self, eng, layer, capacity_blocks=0):
+        self.eng, self.voxel_size = eng, layer.voxel_size
+        self.h = C.c_void_p()
+        eng.check(eng.fn("obs_create")(layer.h, C.c_uint64(capacity_blocks), C.byref(self.h)), "obs_create")
+
+    def close(self):
+        if self.h:
+            self.eng.fn("obs_destroy", None)(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self):
+        self.eng.check(self.eng.fn("obs_clear")(self.h), "obs_clear")
+
+    def set_auto_grow(self, on):
+        self.eng.check(self.eng.fn("obs_set_auto_grow")(self.h, C.c_int(int(on))), "obs_set_auto_grow")
+
+    def set_frame(self, frame_id):
+        """The id (0..255) under which clouds are recorded until it is changed."""
+        self.eng.check(self.eng.fn("obs_set_frame")(self.h, C.c_uint32(int(frame_id))), "obs_set_frame")
+
+    def record(self, T_G_C, xyz, min_ray, max_ray, freespace=False, allow_clear=True):
+        """Record one host cloud (points in the sensor frame); returns when it is recorded."""
+        T = np.ascontiguousarray(T_G_C, np.float32)
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        self.eng.check(self.eng.fn("obs_record")(self.h, _fp(T), _fp(xyz), C.c_uint64(len(xyz)), C.c_int(int(freespace)), C.c_float(min_ray),
+                                                 C.c_float(max_ray), C.c_int(int(allow_clear))), "obs_record")
+
+    def record_dev(self, T_G_C, xyz, min_ray, max_ray, n=None, freespace=False, allow_clear=True, stream=None):
+        """cox_obs_record_dev: xyz a torch tensor on the record's GPU or a raw device pointer (int; then n is required), ordered
+        against `stream` (a torch stream, a raw hipStream_t or None = the null stream); not waited for."""
+        T = np.ascontiguousarray(T_G_C, np.float32)
+        if n is None:
+            n = xyz.numel() // 3
+        ptr = xyz.data_ptr() if hasattr(xyz, "data_ptr") else int(xyz)
+        s = getattr(stream, "cuda_stream", stream)
+        self.eng.check(self.eng.fn("obs_record_dev")(self.h, _fp(T), C.c_void_p(ptr), C.c_uint64(n), C.c_int(int(freespace)), C.c_float(min_ray),
+                                                     C.c_float(max_ray), C.c_int(int(allow_clear)), C.c_void_p(s or 0)), "obs_record_dev")
+
+    def sync(self):
+        """Wait for the records; raises CoxError (COX_ERR_POOL_EXHAUSTED ...) when marks were lost since the last call."""
+        self.eng.check(self.eng.fn("obs_sync")(self.h), "obs_sync")
+
+    def stats(self):
+        """dict(blocks, marked_cells, bytes)."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self.eng.check(self.eng.fn("obs_stats")(self.h, C.byref(a), C.byref(b), C.byref(c)), "obs_stats")
+        return dict(blocks=int(a.value), marked_cells=int(b.value), bytes=int(c.value))
+
+    def counts(self):
+        """Running totals: (points that marked, atomic ORs left after the lanes of a wave that share a cell merged)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self.eng.check(self.eng.fn("obs_counts")(self.h, C.byref(a), C.byref(b)), "obs_counts")
+        return int(a.value), int(b.value)
+
+    def download(self):
+        """(block_index int32[n,3] in (z, y, x) order, masks uint32[n,64,8])."""
+        n = C.c_uint64()
+        f = self.eng.fn("obs_download")
+        self.eng.check(f(self.h, None, None, C.c_uint64(0), C.byref(n)), "obs_download(query)")
+        nb = int(n.value)
+        idx = np.zeros((nb, 3), np.int32)
+        masks = np.zeros((nb, self.CELLS, self.WORDS), np.uint32)
+        if nb:
+            self.eng.check(f(self.h, _fp(idx), _fp(masks), C.c_uint64(nb), C.byref(n)), "obs_download")
+        return idx, masks
 
 
 class RegPoints:
@@ -789,12 +873,37 @@ class MeshLayer:
                        "meshlayer_msg")
         return out
 
+    def history(self, obs, with_time=False):
+        """cox_meshlayer_history against an ObservationHistory: dict(history_begin uint64[nt + 1], history uint32[...] of
+        inclusive [first, last] frame-id runs, block_has_history uint8[nb]) in cox_mesh_msg's layout."""
+        nt, nh, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        self.eng.check(self.eng.fn("meshlayer_history_size")(self.h, obs.h, C.byref(nt), C.byref(nh), C.byref(ms)), "meshlayer_history_size")
+        nt, nh = int(nt.value), int(nh.value)
+        out = dict(history_begin=np.zeros(nt + 1, np.uint64), history=np.zeros(nh, np.uint32), block_has_history=np.zeros(self.n_blocks, np.uint8))
+        self.eng.check(self.eng.fn("meshlayer_history")(self.h, obs.h, _fp(out["history_begin"]), _fp(out["history"]), _fp(out["block_has_history"]),
+                                                        C.c_uint64(nt), C.c_uint64(nh), C.c_uint64(self.n_blocks)), "meshlayer_history")
+        if with_time:
+            out["kernel_ms"] = float(ms.value)
+        return out
+
     def to_msg(self, color_mode="color", history=None, trajectory=()):
-        """A voxblox_msgs/Mesh in the dict form MeshMsg takes: MeshMsg(**mesh.to_msg(...)).  history: None, or a callable
-        (block index tuple, n_triangles) -> one run-length list per triangle (the caller's observation histories)."""
+        """A voxblox_msgs/Mesh in the dict form MeshMsg takes: MeshMsg(**mesh.to_msg(...)).  history: None, a callable
+        (block index tuple, n_triangles) -> one run-length list per triangle (the caller's observation histories), or an
+        ObservationHistory recorded while the layer was fused (a block none of whose triangles was seen goes without history)."""
         d = self.download()
         a = self.msg_arrays(color_mode)
         vb = d["vertex_begin"].astype(np.int64)
+        if isinstance(history, ObservationHistory):
+            h = self.history(history)
+            hb, runs, has = h["history_begin"].astype(np.int64), h["history"], h["block_has_history"]
+            order = {tuple(int(v) for v in d["block_index"][k]): k for k in range(self.n_blocks)}
+
+            def history(idx, n, _hb=hb, _runs=runs, _has=has, _vb=vb, _order=order):
+                k = _order[idx]
+                if not _has[k]:
+                    return None
+                t0 = int(_vb[k]) // 3
+                return [_runs[_hb[t]:_hb[t + 1]].tolist() for t in range(t0, t0 + n)]
         blocks = []
         for k in range(self.n_blocks):
             s, e = vb[k], vb[k + 1]

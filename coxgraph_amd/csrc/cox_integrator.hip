@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/coxgraph_hip_history.h"
 #include "cox_internal.hpp"
 #include "cox_plan.hpp"
 #include "cox_sort.hpp"
@@ -201,6 +202,12 @@ struct cox_integrator {
   hipEvent_t in_ready[kInputSets] = {};  // staging set k has been filled (the frame's first stage waits for it)
   hipEvent_t in_free[kInputSets] = {};   // the frame that read staging set k last has read it for the last time
   bool in_used[kInputSets] = {};
+  // observation record (cox_integrator_attach_history): every cloud is also marked in it, from the same device copy, on the record's
+  // own stream -- beside the frame's ray generation, which therefore waits for nothing new
+  cox_obs* obs = nullptr;
+  hipEvent_t obs_read[kInputSets] = {};  // the record has read staging set k (created with the first attach)
+  bool obs_used[kInputSets] = {};
+  hipEvent_t ev_obs_read = nullptr;      // ... the caller's device buffer (cox_integrate_points_dev)
   float* pin_xyz[kInputSets] = {};       // pinned bounce buffers for pageable host inputs (a pinned caller buffer is copied from directly)
   uint8_t* pin_rgba[kInputSets] = {};
   u32 pin_cap = 0;
@@ -293,6 +300,7 @@ static int sync_all(cox_integrator* I) {
     if (I->st[k] && (k == 0 || I->st[k] != I->st[k - 1])) COX_HIP(hipStreamSynchronize(I->st[k]));
   if (I->st_alt) COX_HIP(hipStreamSynchronize(I->st_alt));
   if (I->st_in) COX_HIP(hipStreamSynchronize(I->st_in));
+  if (I->obs) COX_TRY(cox_internal_obs_wait(I->obs));  // (it reads the frames' input buffers)
   return COX_OK;
 }
 
@@ -957,6 +965,7 @@ static int follow_layer(cox_integrator* I) {
 struct FrameInput {
   hipEvent_t ready = nullptr, consumed = nullptr;
   const u32* n_dev = nullptr;
+  int staging_set = -1;  // the staging set the inputs are in (an attached observation record orders itself against its events)
 };
 // enqueue the whole frame; xyz / rgba are device pointers that must stay valid until the frame's stage M is done
 static int integrate_device(cox_integrator* I, const float T[7], const float* xyz, const uint8_t* rgba, u32 n, int freespace, bool caller_waits = false,
@@ -1009,6 +1018,14 @@ static int integrate_device(cox_integrator* I, const float T[7], const float* xy
     COX_HIP(hipStreamWaitEvent(stage_stream(I, 0, slot), I->ev_producer, 0));
   }
   if (in.ready) COX_HIP(hipStreamWaitEvent(stage_stream(I, 0, slot), in.ready, 0));
+  if (I->obs && n) {  // the record marks the same cloud on its own stream: behind the inputs' producer, beside everything else
+    const int k = in.staging_set;
+    hipEvent_t read = k >= 0 ? I->obs_read[k] : I->ev_obs_read;
+    COX_TRY(cox_internal_obs_record(I->obs, T, xyz, n, freespace, I->cfg.min_ray_length_m, I->cfg.max_ray_length_m, I->cfg.allow_clear,
+                                    I->has_producer ? I->ev_producer : nullptr, k >= 0 ? I->in_ready[k] : nullptr, read, false));
+    if (k >= 0) I->obs_used[k] = true;
+    if (I->has_producer) COX_HIP(hipStreamWaitEvent(I->producer, read, 0));  // the caller's stream may overwrite / free the cloud after that
+  }
   if (I->method == COX_METHOD_FAST) {  // front on st[0] (this thread), solve on st[1] and update on st[3] (submission thread): fast_front / fast_solve
     if (F.used) COX_HIP(hipStreamWaitEvent(I->st[0], F.done, 0));  // frame t-6 is done with this frame set
     FastJob job;
@@ -1402,8 +1419,10 @@ static int wait_staging_set_free(cox_integrator* I, int k, hipStream_t s_in) {
   if (!I->in_used[k]) return COX_OK;
   if (s_in == I->st_in) {
     COX_HIP(hipEventSynchronize(I->in_free[k]));
+    if (I->obs_used[k]) COX_HIP(hipEventSynchronize(I->obs_read[k]));
   } else {
     COX_HIP(hipStreamWaitEvent(s_in, I->in_free[k], 0));
+    if (I->obs_used[k]) COX_HIP(hipStreamWaitEvent(s_in, I->obs_read[k], 0));
   }
   return COX_OK;
 }
@@ -1443,6 +1462,7 @@ static int stage_host_inputs(cox_integrator* I, int k, const void* a, size_t a_b
   I->in_used[k] = true;
   in->ready = I->st_in ? I->in_ready[k] : nullptr;  // (without an input stream: same stream as the frame's first stage, stream order)
   in->consumed = I->in_free[k];
+  in->staging_set = k;
   return COX_OK;
 }
 
@@ -1464,6 +1484,7 @@ int cox_integrate_points(cox_integrator_t* I, const float T_G_C[7], const float*
     I->in_used[k] = true;
     in.ready = I->st_in ? I->in_ready[k] : nullptr;
     in.consumed = I->in_free[k];
+    in.staging_set = k;
   }
   COX_TRY(integrate_device(I, T_G_C, I->own_xyz[k], rgba ? I->own_rgba[k] : nullptr, static_cast<u32>(n), freespace, true, in));
   return integrator_finish(I);
@@ -1511,6 +1532,7 @@ int cox_integrate_depth_dev(cox_integrator_t* I, const float T_G_C[7], const flo
   COX_ENTRY_NO_DRAIN();
   if (!I || !T_G_C || !depth_dev || !K || w <= 0 || h <= 0 || static_cast<uint64_t>(w) * h > 0x7FFFFFFFull) return COX_ERR_INVALID_ARG;
   if (I->proj) return COX_ERR_UNSUPPORTED;  // the projective integrator takes point clouds (it builds its own range image)
+  if (I->obs) return COX_ERR_UNSUPPORTED;   // a history records point clouds (the depth front end keeps its point list to itself)
   COX_HIP(hipSetDevice(I->layer->device));
   const u32 n = static_cast<u32>(w) * static_cast<u32>(h);
   COX_TRY(ensure_capacity(I, n));
@@ -1546,7 +1568,7 @@ int cox_integrate_depth_dev(cox_integrator_t* I, const float T_G_C[7], const flo
 int cox_integrate_depth_async(cox_integrator_t* I, const float T_G_C[7], const float* depth, const uint8_t* rgba, int w, int h, const float K[4]) {
   COX_ENTRY_NO_DRAIN();
   if (!I || !T_G_C || !depth || !K || w <= 0 || h <= 0 || static_cast<uint64_t>(w) * h > 0x7FFFFFFFull) return COX_ERR_INVALID_ARG;
-  if (I->proj) return COX_ERR_UNSUPPORTED;
+  if (I->proj || I->obs) return COX_ERR_UNSUPPORTED;
   COX_HIP(hipSetDevice(I->layer->device));
   const u32 n = static_cast<u32>(w) * static_cast<u32>(h);
   COX_TRY(ensure_capacity(I, n));
@@ -1578,6 +1600,22 @@ int cox_integrator_set_input_stream(cox_integrator_t* I, void* hip_stream, int e
   if (!I) return COX_ERR_INVALID_ARG;
   I->has_producer = enable != 0;
   I->producer = static_cast<hipStream_t>(hip_stream);
+  return COX_OK;
+}
+
+int cox_integrator_attach_history(cox_integrator_t* I, cox_obs_t* obs) {
+  COX_ENTRY();
+  if (!I) return COX_ERR_INVALID_ARG;
+  if (obs && !cox_internal_obs_matches(obs, I->layer)) return COX_ERR_INVALID_ARG;
+  COX_HIP(hipSetDevice(I->layer->device));
+  if (I->proj) return cox_proj_attach_history(I->proj, obs);
+  COX_TRY(sync_all(I));  // the record that is attached so far has read every cloud handed to it
+  if (obs && !I->ev_obs_read) {
+    COX_TRY(make_event(I, &I->ev_obs_read));
+    for (hipEvent_t& e : I->obs_read) COX_TRY(make_event(I, &e));
+  }
+  I->obs = obs;
+  for (bool& u : I->obs_used) u = false;
   return COX_OK;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdio>
 #include <cstdlib>
+#include <vector>
 
 #include "../../include/coxgraph_hip.h"
 #include "cox_device.hpp"
@@ -107,6 +108,31 @@ struct cox_regpoints {
   u64 cum_total = 0;
 };
 
+// voxblox::MeshLayer of a TSDF layer (cox_mesher.hip builds it, cox_history.hip reads it)
+struct cox_meshlayer {
+  int device = 0;
+  float voxel_size = 0, block_edge = 0;
+  u64 n_blocks = 0, n_vertices = 0;
+  std::vector<int32_t> block_index;  // 3 per block
+  std::vector<u64> vertex_begin;     // n_blocks + 1
+  float* pos = nullptr;              // 3 per vertex
+  float* nrm = nullptr;              // 3 per vertex
+  uint8_t* rgb = nullptr;            // 3 per vertex
+  u64 n_color_missing = 0;
+  double kernel_ms[2] = {0.0, 0.0};
+  bool transformed = false;          // cox_meshlayer_transform has moved it out of the layer's frame
+};
+
+// observation record of a submap (cox_history.hip).  An integrator it is attached to hands it every cloud it fuses:
+// cox_internal_obs_record enqueues the marks on the record's own stream behind the events wait_a / wait_b (either may be null) and
+// records read_done (may be null) once the cloud has been read; nothing is waited for on the host unless settle is set (then the
+// block count of the previous record is awaited first, so that the pool grows before it can run out).
+struct cox_obs;
+int cox_internal_obs_record(cox_obs* O, const float T[7], const float* xyz_dev, u32 n, int freespace, float min_ray, float max_ray, int allow_clear,
+                            hipEvent_t wait_a, hipEvent_t wait_b, hipEvent_t read_done, bool settle);
+int cox_internal_obs_wait(cox_obs* O);  // every record enqueued so far has run (errors stay in the record)
+bool cox_internal_obs_matches(const cox_obs* O, const cox_layer* L);
+
 // hipGetLastError() is a per-thread sticky slot shared with every other HIP user in the process
 // (PyTorch probes peers / devices during its lazy init and may leave a benign error behind).  Every
 // entry point clears it first so that the check after our own launches only sees our own errors.
@@ -141,3 +167,4 @@ int cox_proj_integrate(cox_projective* P, const float T[7], const float* xyz_dev
 int cox_proj_integrate_host(cox_projective* P, const float T[7], const float* xyz, uint64_t n, int deintegrate);
 int cox_proj_sync(cox_projective* P);
 int cox_proj_last_stats(cox_projective* P, cox_frame_stats* out);
+int cox_proj_attach_history(cox_projective* P, cox_obs* obs);

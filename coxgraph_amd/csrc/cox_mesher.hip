@@ -30,19 +30,6 @@
 
 using namespace cox;
 
-struct cox_meshlayer {
-  int device = 0;
-  float voxel_size = 0, block_edge = 0;
-  u64 n_blocks = 0, n_vertices = 0;
-  std::vector<int32_t> block_index;  // 3 per block
-  std::vector<u64> vertex_begin;     // n_blocks + 1
-  float* pos = nullptr;              // 3 per vertex
-  float* nrm = nullptr;              // 3 per vertex
-  uint8_t* rgb = nullptr;            // 3 per vertex
-  u64 n_color_missing = 0;
-  double kernel_ms[2] = {0.0, 0.0};
-};
-
 struct cox_meshconn {
   int device = 0;
   u64 n_vertices = 0, n_triangles = 0;
@@ -685,6 +672,7 @@ int cox_meshlayer_transform(cox_meshlayer_t* M, const float T[7]) {
   hipLaunchKernelGGL(k_mesh_transform, dim3(grid), dim3(256), 0, nullptr, M->pos, M->nrm, M->rgb, M->n_vertices, X, 1, M->pos, M->nrm,
                      static_cast<uint8_t*>(nullptr));
   if (hipStreamSynchronize(nullptr) != hipSuccess || hipGetLastError() != hipSuccess) return COX_ERR_NO_DEVICE;
+  M->transformed = true;
   return COX_OK;
 }
 

@@ -329,6 +329,9 @@ struct cox_projective {
     int deintegrate;
   } inflight[4] = {};
   int deferred = COX_OK;  // what settling on behalf of another writer ended with: reported by this integrator's next call
+  // observation record (cox_integrator_attach_history): marks every integrated cloud on its own stream, behind ev_obs
+  cox_obs* obs = nullptr;
+  hipEvent_t ev_obs = nullptr;
 };
 
 #define COX_TRY(expr)              \
@@ -352,6 +355,8 @@ void cox_proj_destroy(cox_projective* P) {
   if (P->h_stall) (void)hipHostFree(P->h_stall);
   for (hipEvent_t e : P->ring)
     if (e) (void)hipEventDestroy(e);
+  if (P->obs) (void)cox_internal_obs_wait(P->obs);
+  if (P->ev_obs) (void)hipEventDestroy(P->ev_obs);
   if (P->stream) (void)hipStreamDestroy(P->stream);
   delete P;
 }
@@ -452,6 +457,7 @@ static inline int proj_take_deferred(cox_projective* P) {
 static int proj_finish(cox_projective* P) {
   COX_TRY(proj_take_deferred(P));
   COX_HIP(hipStreamSynchronize(P->stream));
+  if (P->obs) COX_TRY(cox_internal_obs_wait(P->obs));  // (it reads the frames' clouds)
   if (P->h_stall[0] != 0u) COX_TRY(proj_recover(P));
   if (P->pending) {
     const ProjCounters& c = *P->h_cnt;
@@ -586,7 +592,19 @@ int cox_proj_integrate(cox_projective* P, const float T[7], const float* xyz_dev
     P->last = cox_frame_stats{};
     return COX_OK;
   }
+  if (P->obs && !deintegrate) {  // (deintegration does not unmark)
+    COX_HIP(hipEventRecord(P->ev_obs, s));  // behind the upload of a host cloud
+    COX_TRY(cox_internal_obs_record(P->obs, T, xyz_dev, static_cast<u32>(n), 0, P->cfg.min_ray_length_m, P->cfg.max_ray_length_m, P->cfg.allow_clear, P->ev_obs, nullptr,
+                                    nullptr, false));
+  }
   return proj_enqueue(P, T, xyz_dev, n, deintegrate);
+}
+
+int cox_proj_attach_history(cox_projective* P, cox_obs* obs) {
+  COX_TRY(proj_finish(P));
+  if (obs && !P->ev_obs && hipEventCreateWithFlags(&P->ev_obs, hipEventDisableTiming) != hipSuccess) return COX_ERR_NO_DEVICE;
+  P->obs = obs;
+  return COX_OK;
 }
 
 int cox_proj_integrate_host(cox_projective* P, const float T[7], const float* xyz, uint64_t n, int deintegrate) {

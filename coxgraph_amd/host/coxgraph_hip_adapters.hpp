@@ -7,12 +7,14 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <cmath>
 #include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../../include/coxgraph_hip.h"
+#include "../../include/coxgraph_hip_history.h"
 
 namespace coxgraph_hip {
 
@@ -139,6 +141,43 @@ struct TsdfIntegratorConfig : cox_tsdf_config {
   TsdfIntegratorConfig() { cox_tsdf_config_default(this); }
 };
 
+// Which frames saw which part of a submap (cox_obs_t): filled by the integrator it is set on, read by generateSubmapMeshMsg's
+// history overload (coxgraph_hip_mesh.hpp).  Frame ids are the consumer's keys, round((stamp - stamp0) / 0.05) (mesh_converter.h:194-199).
+class ObservationHistory {
+ public:
+  using Ptr = std::shared_ptr<ObservationHistory>;
+  explicit ObservationHistory(const TsdfLayer& geometry, uint64_t capacity_blocks = 0) { check(cox_obs_create(geometry.handle(), capacity_blocks, &h_), "ObservationHistory"); }
+  ~ObservationHistory() { cox_obs_destroy(h_); }
+  ObservationHistory(const ObservationHistory&) = delete;
+  ObservationHistory& operator=(const ObservationHistory&) = delete;
+  void clear() {  // the submap was cut (next to removeAllBlocks); the next stamp starts a new submap's ids
+    check(cox_obs_clear(h_), "ObservationHistory::clear");
+    has_stamp0_ = false;
+  }
+  // the id of the frame stamped (sec, nsec): 0 for the first stamp since construction / clear
+  uint32_t frameIdOf(uint32_t sec, uint32_t nsec) {
+    if (!has_stamp0_) sec0_ = sec, nsec0_ = nsec, has_stamp0_ = true;
+    if (sec == sec0_ && nsec == nsec0_) return 0;
+    const double dt = (static_cast<double>(sec) - static_cast<double>(sec0_)) + (static_cast<double>(nsec) - static_cast<double>(nsec0_)) * 1e-9;
+    const double id = std::round(dt / 0.05);
+    if (!(id >= 0.0 && id < 4294967295.0)) return 0xFFFFFFFFu;  // (refused by setFrame)
+    return static_cast<uint32_t>(id);
+  }
+  void setFrame(uint32_t frame_id) { check(cox_obs_set_frame(h_, frame_id), "ObservationHistory::setFrame"); }  // ids above 255 throw
+  void sync() { check(cox_obs_sync(h_), "ObservationHistory::sync"); }
+  size_t getNumberOfAllocatedBlocks() const {
+    uint64_t n = 0;
+    check(cox_obs_stats(h_, &n, nullptr, nullptr), "ObservationHistory");
+    return n;
+  }
+  cox_obs_t* handle() const { return h_; }
+
+ private:
+  cox_obs_t* h_ = nullptr;
+  bool has_stamp0_ = false;
+  uint32_t sec0_ = 0, nsec0_ = 0;
+};
+
 // voxblox::TsdfIntegratorBase + TsdfIntegratorFactory
 class TsdfIntegrator {
  public:
@@ -154,6 +193,15 @@ class TsdfIntegrator {
     return Ptr(new TsdfIntegrator(m, config, layer));
   }
   ~TsdfIntegrator() { cox_integrator_destroy(h_); }
+  // Every cloud integrated from now on is also recorded in `history` (nullptr: no longer), under the frame id of the stamp
+  // handed to setFrameStamp before the cloud.
+  void setObservationHistory(const ObservationHistory::Ptr& history) {
+    check(cox_integrator_attach_history(h_, history ? history->handle() : nullptr), "setObservationHistory");
+    history_ = history;
+  }
+  void setFrameStamp(uint32_t sec, uint32_t nsec) {
+    if (history_) history_->setFrame(history_->frameIdOf(sec, nsec));
+  }
   // TsdfIntegratorBase::integratePointCloud(T_G_C, points_C, colors, freespace_points)
   void integratePointCloud(const Transformation& T_G_C, const Pointcloud& points_C, const Colors& colors, const bool freespace_points = false) {
     if (!colors.empty() && colors.size() != points_C.size()) throw std::runtime_error("integratePointCloud: points_C.size() != colors.size()");
@@ -186,6 +234,7 @@ class TsdfIntegrator {
  private:
   TsdfIntegrator(int method, const TsdfIntegratorConfig& config, TsdfLayer* layer) { check(cox_integrator_create(layer->handle(), &config, method, &h_), "TsdfIntegrator"); }
   cox_integrator_t* h_ = nullptr;
+  ObservationHistory::Ptr history_;
 };
 
 // ---- recover mode ---------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/coxgraph_hip_history.h"
 #include "../../include/coxgraph_hip_mesh.h"
 #include "coxgraph_hip_submap.hpp"
 
@@ -42,7 +43,7 @@ class MeshLayer {
 };
 
 // The message is recover mode's MeshMsg (coxgraph_hip_adapters.hpp): generateVoxbloxMeshMsg fills block_edge_length and the
-// blocks' index / x y z / r g b; histories and the trajectory stay the caller's.
+// blocks' index / x y z / r g b; fillMeshHistories adds the histories of an ObservationHistory; the trajectory stays the caller's.
 enum class ColorMode { kColor = COX_MESH_COLOR, kNormals = COX_MESH_NORMALS, kGray = COX_MESH_GRAY, kLambert = COX_MESH_LAMBERT, kLambertColor = COX_MESH_LAMBERT_COLOR };
 
 // voxblox::Mesh after createConnectedMesh: welded vertices, triangles as index triples
@@ -78,6 +79,30 @@ inline void generateVoxbloxMeshMsg(const MeshLayer& mesh_layer, ColorMode color_
     m.g.assign(g.begin() + s, g.begin() + e);
     m.b.assign(b.begin() + s, b.begin() + e);
   }
+}
+
+// the per-triangle observation histories of mesh_layer (still in its layer's frame) into a message generateVoxbloxMeshMsg has
+// filled from it; a block none of whose triangles was seen keeps an empty history (recover mode skips it)
+inline void fillMeshHistories(const MeshLayer& mesh_layer, const ObservationHistory& history, MeshMsg* msg) {
+  uint64_t nt = 0, nh = 0;
+  check(cox_meshlayer_history_size(mesh_layer.handle(), history.handle(), &nt, &nh, nullptr), "fillMeshHistories");
+  const size_t nb = msg->mesh_blocks.size();
+  std::vector<uint64_t> begin(nt + 1);
+  std::vector<uint32_t> runs(nh);
+  std::vector<uint8_t> has(nb);
+  check(cox_meshlayer_history(mesh_layer.handle(), history.handle(), begin.data(), runs.data(), has.data(), nt, nh, nb), "fillMeshHistories");
+  uint64_t t = 0;
+  for (size_t k = 0; k < nb; ++k) {
+    MeshBlockMsg& m = msg->mesh_blocks[k];
+    const size_t n = m.x.size() / 3;
+    m.history.clear();
+    if (has[k]) {
+      m.history.resize(n);
+      for (size_t i = 0; i < n; ++i) m.history[i].assign(runs.begin() + begin[t + i], runs.begin() + begin[t + i + 1]);
+    }
+    t += n;
+  }
+  if (t != nt) throw std::runtime_error("fillMeshHistories: the message is not this mesh layer's");
 }
 
 // createConnectedMesh over several mesh layers, each moved by its pose first
@@ -148,6 +173,11 @@ class SubmapVisuals {
   void generateSubmapMeshMsg(const MeshLayer::Ptr& mesh_layer_ptr, ColorMode color_mode, MeshMsg* mesh_msg) const {
     if (!mesh_layer_ptr || !mesh_msg) throw std::runtime_error("generateSubmapMeshMsg: null argument");
     generateVoxbloxMeshMsg(*mesh_layer_ptr, color_mode, mesh_msg);
+  }
+  // publish_mesh_with_history (tsdf_client.launch:19,46): the message with the histories recorded while the submap was fused
+  void generateSubmapMeshMsg(const MeshLayer::Ptr& mesh_layer_ptr, const ObservationHistory& history, MeshMsg* mesh_msg) const {
+    generateSubmapMeshMsg(mesh_layer_ptr, config_.color_mode, mesh_msg);
+    fillMeshHistories(*mesh_layer_ptr, history, mesh_msg);
   }
 
  private:
