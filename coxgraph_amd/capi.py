@@ -18,6 +18,7 @@ STATUS = {
 METHODS = {"simple": 0, "merged": 1, "fast": 2, "projective": 3}
 QUERY_MODES = {"nearest": 0, "interpolate": 1, "adaptive": 2}  # cox_query_mode (include/coxgraph_hip_map.h)
 Q_VALUE, Q_TRILINEAR, Q_GRADIENT = 1, 2, 4
+R_HIT, R_NORMAL, R_COLOR, R_BUDGET = 1, 2, 4, 8  # status bits of a rendered pixel (include/coxgraph_hip_render.h)
 VOXELS_PER_BLOCK = 4096
 
 
@@ -56,6 +57,19 @@ class FrameStats(C.Structure):
 class EsdfConfig(C.Structure):
     """cox_esdf_config (voxblox EsdfIntegrator::Config)."""
     _fields_ = [("max_distance_m", C.c_float), ("min_distance_m", C.c_float), ("default_distance_m", C.c_float), ("min_weight", C.c_float)]
+
+
+class RenderConfig(C.Structure):
+    """cox_render_config."""
+    _fields_ = [("min_depth", C.c_float), ("max_depth", C.c_float), ("step_scale", C.c_float), ("min_step_voxels", C.c_float),
+                ("max_samples", C.c_uint32)]
+
+
+class RenderStats(C.Structure):
+    _fields_ = [("n_hits", C.c_uint64), ("n_samples", C.c_uint64), ("n_block_skips", C.c_uint64), ("n_budget", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class RegConfig(C.Structure):
@@ -244,6 +258,50 @@ class Layer:
         s = getattr(stream, "cuda_stream", stream)
         self.eng.check(self.eng.fn("layer_query_dev")(self.h, ptr(xyz), C.c_uint64(n), C.c_int(QUERY_MODES[mode]), C.c_int(int(gradient)), ptr(distance),
                                                       ptr(weight), ptr(grad), ptr(status), C.c_void_p(s or 0)), "layer_query_dev")
+
+    # ---- rendering (include/coxgraph_hip_render.h) ----
+    def _render_args(self, T_G_C, w, h, K, cfg):
+        T = np.ascontiguousarray(T_G_C, np.float32)
+        assert T.shape == (7,)
+        if K is None:
+            from . import synth
+            K = synth.INTRINSICS[(w, h)]
+        K = np.ascontiguousarray(K, np.float32)
+        assert K.shape == (4,)
+        c = RenderConfig()
+        self.eng.fn("render_config_default", None)(C.byref(c))
+        for k, v in cfg.items():
+            if not hasattr(c, k):
+                raise AttributeError(k)
+            setattr(c, k, v)
+        return T, K, c
+
+    def render(self, T_G_C, w, h, K=None, **cfg):
+        """Depth, normal and colour images of the layer seen from T_G_C through a w x h pinhole camera K = (fx, fy, cx, cy)
+        (cox_layer_render; K None: synth.INTRINSICS[(w, h)]; cfg: fields of cox_render_config): dict(depth[h,w] z-depth,
+        normal[h,w,3], rgba[h,w,4], status[h,w] uint8 of R_HIT | R_NORMAL | R_COLOR | R_BUDGET, stats); NaN / 0 where the
+        matching status bit is clear."""
+        T, K, c = self._render_args(T_G_C, w, h, K, cfg)
+        out = dict(depth=np.empty((h, w), np.float32), normal=np.empty((h, w, 3), np.float32), rgba=np.empty((h, w, 4), np.uint8),
+                   status=np.empty((h, w), np.uint8))
+        st = RenderStats()
+        self.eng.check(self.eng.fn("layer_render")(self.h, _fp(T), C.c_int(w), C.c_int(h), _fp(K), C.byref(c), _fp(out["depth"]), _fp(out["normal"]),
+                                                   _fp(out["rgba"]), _fp(out["status"]), C.byref(st)), "layer_render")
+        out["stats"] = st.asdict()
+        return out
+
+    def render_dev(self, T_G_C, w, h, K=None, depth=None, normal=None, rgba=None, status=None, stream=None, **cfg):
+        """cox_layer_render_dev: outputs are torch tensors on the layer's GPU or raw device pointers (ints), any of them None;
+        enqueued on `stream` (a torch stream, a raw hipStream_t or None = the null stream), not waited for.  Every pixel of
+        every buffer given is written."""
+        def ptr(t):
+            if t is None:
+                return None
+            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        T, K, c = self._render_args(T_G_C, w, h, K, cfg)
+        s = getattr(stream, "cuda_stream", stream)
+        self.eng.check(self.eng.fn("layer_render_dev")(self.h, _fp(T), C.c_int(w), C.c_int(h), _fp(K), C.byref(c), ptr(depth), ptr(normal), ptr(rgba),
+                                                       ptr(status), C.c_void_p(s or 0)), "layer_render_dev")
 
     def free_points(self, min_distance):
         """createFreePointcloudFromEsdfLayer: (xyz float32[n,3] voxel centres, intensity float32[n] distances), blocks in download

@@ -1,0 +1,455 @@
+// MI355X (gfx950): depth, normal and colour images of a layer seen from a pose, behind include/coxgraph_hip_render.h.
+//
+//   k_render  one lane per pixel, one wave per 8 x 8 pixel tile (a workgroup is 16 x 16 pixels): neighbouring lanes walk
+//             neighbouring rays, so their voxel loads share cache lines and their block lookups hit the same hash slots.  A ray
+//             is sphere-traced through the layer: a sample is the ADAPTIVE distance of the map queries (trilinear through
+//             interp_cell / interp_member of cox_interp.hpp, else the containing voxel), the next step is |d| * step_scale, an
+//             unallocated block is left through its far face in one step, and a positive sample followed by a non-positive one
+//             is the hit, placed by one linear interpolation.  The blocks around a sample are resolved through a per-lane
+//             cache of the last 2 x 2 x 2 block set (consecutive samples of a ray mostly stay inside it); whatever the cache
+//             does not hold is looked up in the hash table, so the cache never changes an answer.  Lanes do not wait for each
+//             other: a wave ends when its longest ray does.
+//
+// Rules and arithmetic: DESIGN.md section 7g.  The float expressions are those of tests/cpp/render_reference.cpp, one by one.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "../../include/coxgraph_hip_render.h"
+#include "cox_internal.hpp"
+#include "cox_interp.hpp"
+
+using namespace cox;
+
+namespace {
+
+#define COX_TRY(expr)              \
+  do {                             \
+    int st_ = (expr);              \
+    if (st_ != COX_OK) return st_; \
+  } while (0)
+
+template <typename T>
+struct DevBuf {  // frees on scope exit
+  T* p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  int alloc(size_t count) {
+    if (count == 0) count = 1;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      return e == hipErrorOutOfMemory ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
+    }
+    return COX_OK;
+  }
+};
+
+struct EventPair {  // destroys on scope exit
+  hipEvent_t a = nullptr, b = nullptr;
+  ~EventPair() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+};
+
+int device_present() {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
+    (void)hipGetLastError();
+    return COX_ERR_NO_DEVICE;
+  }
+  return COX_OK;
+}
+
+LayerView layer_view(const cox_layer* L) {
+  return LayerView{L->voxels, L->ht_keys, L->ht_vals, L->ht_cap - 1, L->voxel_size, L->voxel_size_inv, L->block_size, L->block_size_inv};
+}
+
+constexpr int kRenderThreads = 256;  // 4 waves: 2 x 2 tiles of 8 x 8 pixels
+constexpr int kTile = 16;
+
+struct RenderParams {
+  float qw, qx, qy, qz, ox, oy, oz;  // T_G_C
+  float fx, fy, cx, cy;
+  int w, h;
+  u32 tiles_x;
+  float min_depth, max_depth, step_scale;
+  float min_step;    // min_step_voxels * voxel_size
+  float half_voxel;  // 0.5 * voxel_size
+  u32 max_samples;
+};
+
+// Pool indices of the 2 x 2 x 2 blocks from lo on, filled in as the ray asks for them and kept until the ray leaves that set.
+struct RayCache {
+  int lo[3];
+  u32 pool[8];  // (x - lo.x) << 2 | (y - lo.y) << 1 | (z - lo.z); kInvalid when missing
+  u32 have;     // bit c: pool[c] was resolved
+  __device__ __forceinline__ u32 find(const LayerView& L, int x, int y, int z) const {
+    const u32 dx = static_cast<u32>(x - lo[0]), dy = static_cast<u32>(y - lo[1]), dz = static_cast<u32>(z - lo[2]);
+    if (dx <= 1u && dy <= 1u && dz <= 1u) {
+      const u32 sel = (dx << 2) | (dy << 1) | dz;
+      if ((have >> sel) & 1u) {
+        u32 r = pool[0];
+#pragma unroll
+        for (u32 c = 1; c < 8; ++c) r = sel == c ? pool[c] : r;  // no dynamic register indexing (it would go to scratch)
+        return r;
+      }
+    }
+    return HtPool{L}(x, y, z);
+  }
+  // a new corner forgets the set
+  __device__ __forceinline__ void move(const int nlo[3]) {
+    if (nlo[0] != lo[0] || nlo[1] != lo[1] || nlo[2] != lo[2]) {
+      lo[0] = nlo[0], lo[1] = nlo[1], lo[2] = nlo[2];
+      have = 0u;
+    }
+  }
+  // one block of the set (x - lo in 0..1 on every axis): looked up at most once
+  __device__ __forceinline__ u32 own(const LayerView& L, int x, int y, int z) {
+    const u32 sel = (static_cast<u32>(x - lo[0]) << 2) | (static_cast<u32>(y - lo[1]) << 1) | static_cast<u32>(z - lo[2]);
+    if (!((have >> sel) & 1u)) {
+      const u32 p = HtPool{L}(x, y, z);
+#pragma unroll
+      for (u32 c = 0; c < 8; ++c) pool[c] = sel == c ? p : pool[c];
+      have |= 1u << sel;
+    }
+    return find(L, x, y, z);
+  }
+  // the blocks of the set within span (0 or 1 per axis) that are not resolved yet
+  __device__ __forceinline__ void fill(const LayerView& L, const int span[3]) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const int mx = (c >> 2) & 1, my = (c >> 1) & 1, mz = c & 1;
+      if (mx <= span[0] && my <= span[1] && mz <= span[2] && !((have >> c) & 1u)) {
+        pool[c] = HtPool{L}(lo[0] + mx, lo[1] + my, lo[2] + mz);
+        have |= 1u << c;
+      }
+    }
+  }
+};
+
+// what interp_cell asks for blocks with
+struct CachedFind {
+  const LayerView& L;
+  const RayCache& cache;
+  __device__ __forceinline__ u32 operator()(int x, int y, int z) const { return cache.find(L, x, y, z); }
+};
+
+// block of p, and the corner / span of the block set that holds the voxels g - r .. g + r around the voxel g containing p
+__device__ __forceinline__ void block_window(const LayerView& L, const float p[3], int r, int b[3], int lo[3], int span[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    b[k] = grid_index(p[k] * L.block_size_inv);
+    const int v = grid_index((p[k] - static_cast<float>(b[k]) * L.block_size) * L.voxel_size_inv);
+    const int g = b[k] * 16 + (v > 15 ? 15 : (v < 0 ? 0 : v));
+    lo[k] = (g - r) >> 4;
+    span[k] = ((g + r) >> 4) - lo[k];
+  }
+}
+
+__device__ __forceinline__ bool point_in_range(const LayerView& L, const float p[3]) {  // false for NaN and +-inf too
+  return index_in_range(p[0] * L.block_size_inv) && index_in_range(p[1] * L.block_size_inv) && index_in_range(p[2] * L.block_size_inv);
+}
+
+// Interpolator::getInterpDistance at s: false when the cell is incomplete or invalid
+__device__ __forceinline__ bool tri_sample(const LayerView& L, const CachedFind& bc, const float s[3], float* d) {
+  int b[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) b[k] = grid_index(s[k] * L.block_size_inv);
+  if (bc(b[0], b[1], b[2]) == kInvalid) return false;  // getBlockPtrByCoordinates(pos)
+  float dd[8], ww[8], off[3];
+  if (!interp_cell(L, s, b, bc, dd, ww, off)) return false;
+  *d = interp_member(off, dd);
+  return true;
+}
+
+// Block::getVoxelByCoordinates: the voxel of the containing block (grid index clamped into it), nullptr without the block
+__device__ __forceinline__ const u32* containing_voxel(const LayerView& L, const CachedFind& bc, const float s[3]) {
+  int b[3], v[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) b[k] = grid_index(s[k] * L.block_size_inv);
+  const u32 pool = bc(b[0], b[1], b[2]);
+  if (pool == kInvalid) return nullptr;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int g = grid_index((s[k] - static_cast<float>(b[k]) * L.block_size) * L.voxel_size_inv);
+    v[k] = g > 15 ? 15 : (g < 0 ? 0 : g);
+  }
+  return L.voxels + (static_cast<size_t>(pool) * kVoxelsPerBlock + static_cast<u32>(v[0] + 16 * (v[1] + 16 * v[2]))) * kWordsPerVoxel;
+}
+
+// Eigen Quaternion::_transformVector (transform_point of cox_device.hpp without the translation)
+__device__ __forceinline__ F3 rotate(const RenderParams& P, F3 v) {
+  const F3 qv{P.qx, P.qy, P.qz};
+  F3 uv = cross3(qv, v);
+  uv = uv + uv;
+  const F3 c = cross3(qv, uv);
+  return F3{(v.x + P.qw * uv.x) + c.x, (v.y + P.qw * uv.y) + c.y, (v.z + P.qw * uv.z) + c.z};
+}
+
+__global__ void __launch_bounds__(kRenderThreads) k_render(LayerView L, RenderParams P, float* __restrict__ depth, float* __restrict__ normal,
+                                                           u32* __restrict__ rgba, uint8_t* __restrict__ status, unsigned long long* __restrict__ stats) {
+  const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const int u = static_cast<int>((blockIdx.x % P.tiles_x) * kTile + (wave & 1u) * 8u + (lane & 7u));
+  const int v = static_cast<int>((blockIdx.x / P.tiles_x) * kTile + (wave >> 1) * 8u + (lane >> 3));
+  const bool inside = u < P.w && v < P.h;
+  const float nan = __uint_as_float(0x7FC00000u);
+  u32 st = 0u, n_samples = 0u, n_skips = 0u, color = 0u;
+  float t_hit = nan, nrm[3] = {nan, nan, nan};
+  if (inside) {
+    const float xn = (static_cast<float>(u) - P.cx) / P.fx;
+    const float yn = (static_cast<float>(v) - P.cy) / P.fy;
+    const F3 dc{xn, yn, 1.0f};
+    const F3 dg = rotate(P, dc);
+    const float len = sqrtf(dot3(dc, dc));
+    const float o[3] = {P.ox, P.oy, P.oz}, dir[3] = {dg.x, dg.y, dg.z};
+    RayCache cache{{0, 0, 0}, {kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid}, 0u};
+    const CachedFind bc{L, cache};
+    float t = P.min_depth, t_prev = 0.0f, d_prev = 0.0f;
+    bool have_prev = false;
+    while (t <= P.max_depth) {
+      if (n_samples >= P.max_samples) {
+        st = COX_R_BUDGET;
+        break;
+      }
+      ++n_samples;
+      float p[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) p[k] = o[k] + t * dir[k];
+      if (!point_in_range(L, p)) break;  // left the index range (or NaN): a miss
+      int b[3], lo[3], span[3];
+      block_window(L, p, 2, b, lo, span);  // a cell reaches g - 1 .. g + 1, one more voxel for rounding at block faces
+      cache.move(lo);
+      if (cache.own(L, b[0], b[1], b[2]) == kInvalid) {
+        // nothing here: leave the block through its far face, plus half a voxel
+        have_prev = false;
+        ++n_skips;
+        float t_exit = __uint_as_float(0x7F800000u);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          if (dir[k] != 0.0f) {
+            const float face = static_cast<float>(dir[k] > 0.0f ? b[k] + 1 : b[k]) * L.block_size;
+            t_exit = std_min(t_exit, (face - o[k]) / dir[k]);
+          }
+        }
+        const float t_new = t_exit + P.half_voxel / len;
+        t = t_new > t ? t_new : t + L.voxel_size / len;  // always forward
+        continue;
+      }
+      cache.fill(L, span);
+      float d = 0.0f;
+      bool ok = tri_sample(L, bc, p, &d);
+      if (!ok) {
+        const u32* vox = containing_voxel(L, bc, p);
+        if (vox != nullptr) {
+          d = __uint_as_float(vox[0]);
+          ok = __uint_as_float(vox[1]) > 0.0f;
+        }
+      }
+      if (!ok) {  // unobserved: nothing to interpolate across
+        have_prev = false;
+        t = t + L.voxel_size / len;
+        continue;
+      }
+      if (have_prev && d_prev > 0.0f && d <= 0.0f) {
+        t_hit = t_prev + ((t - t_prev) * d_prev) / (d_prev - d);
+        st = COX_R_HIT;
+        break;
+      }
+      t_prev = t;
+      d_prev = d;
+      have_prev = true;
+      t = t + std_max(fabsf(d) * P.step_scale, P.min_step) / len;
+    }
+    if (st & COX_R_HIT) {
+      float p[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) p[k] = o[k] + t_hit * dir[k];
+      if (point_in_range(L, p)) {
+        int b[3], lo[3], span[3];
+        block_window(L, p, 3, b, lo, span);  // the gradient samples reach g - 2 .. g + 2
+        cache.move(lo);
+        cache.fill(L, span);
+        const u32* vox = containing_voxel(L, bc, p);
+        if (vox != nullptr) {  // Interpolator::getGradient: getBlockPtrByCoordinates(pos)
+          if (__uint_as_float(vox[1]) > 0.0f) {
+            color = __builtin_bswap32(vox[2]);  // wire word a | b << 8 | g << 16 | r << 24 -> bytes r, g, b, a
+            st |= COX_R_COLOR;
+          }
+          // central differences of the trilinear distance, g_i = ((0 + d(p - h e_i) * -1) + d(p + h e_i)) / (2 h); one copy of
+          // the gather in the code
+          const float h = L.voxel_size, two_h = 2.0f * L.voxel_size;
+          float g[3] = {0.0f, 0.0f, 0.0f}, acc = 0.0f;
+          bool okg = true;
+#pragma unroll 1
+          for (int k = 0; k < 6 && okg; ++k) {
+            const int axis = k >> 1;
+            const bool plus = (k & 1) != 0;
+            const float off = plus ? h : -h;
+            const float s[3] = {axis == 0 ? p[0] + off : p[0] + 0.0f, axis == 1 ? p[1] + off : p[1] + 0.0f, axis == 2 ? p[2] + off : p[2] + 0.0f};
+            float dv = 0.0f;
+            if (!tri_sample(L, bc, s, &dv)) {
+              okg = false;
+            } else if (!plus) {
+              acc = 0.0f + dv * -1.0f;
+            } else {
+              const float gi = (acc + dv) / two_h;
+              g[0] = axis == 0 ? gi : g[0];
+              g[1] = axis == 1 ? gi : g[1];
+              g[2] = axis == 2 ? gi : g[2];
+            }
+          }
+          if (okg) {  // Eigen normalized()
+            const float z = dot3(F3{g[0], g[1], g[2]}, F3{g[0], g[1], g[2]});
+            if (z > 0.0f) {
+              const float s = sqrtf(z);
+              g[0] = g[0] / s, g[1] = g[1] / s, g[2] = g[2] / s;
+            }
+            nrm[0] = g[0], nrm[1] = g[1], nrm[2] = g[2];
+            st |= COX_R_NORMAL;
+          }
+        }
+      }
+    }
+    // every pixel of every image is written, misses included
+    const size_t i = static_cast<size_t>(v) * static_cast<size_t>(P.w) + static_cast<size_t>(u);
+    if (depth) depth[i] = t_hit;
+    if (normal) {
+      normal[3 * i] = nrm[0];
+      normal[3 * i + 1] = nrm[1];
+      normal[3 * i + 2] = nrm[2];
+    }
+    if (rgba) rgba[i] = color;
+    if (status) status[i] = static_cast<uint8_t>(st);
+  }
+  if (stats) {  // the same for every lane; the rays of the wave are all done here
+    u32 a = n_samples, s = n_skips, hh = (st & COX_R_HIT) ? 1u : 0u, bb = (st & COX_R_BUDGET) ? 1u : 0u;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      a += __shfl_xor(a, off);
+      s += __shfl_xor(s, off);
+      hh += __shfl_xor(hh, off);
+      bb += __shfl_xor(bb, off);
+    }
+    if (lane == 0u) {
+      if (hh) atomicAdd(stats + 0, static_cast<unsigned long long>(hh));
+      if (a) atomicAdd(stats + 1, static_cast<unsigned long long>(a));
+      if (s) atomicAdd(stats + 2, static_cast<unsigned long long>(s));
+      if (bb) atomicAdd(stats + 3, static_cast<unsigned long long>(bb));
+    }
+  }
+}
+
+bool all_finite(const float* a, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(a[i])) return false;
+  return true;
+}
+
+int check_render_args(const cox_layer* L, const float* T, int w, int h, const float* K, const cox_render_config* cfg_in, RenderParams* P) {
+  if (!L || !T || !K) return COX_ERR_INVALID_ARG;
+  if (w <= 0 || h <= 0 || static_cast<u64>(w) * static_cast<u64>(h) > 0x7FFFFFFFull) return COX_ERR_INVALID_ARG;
+  if (!all_finite(T, 7) || !all_finite(K, 4) || K[0] == 0.0f || K[1] == 0.0f) return COX_ERR_INVALID_ARG;
+  cox_render_config cfg;
+  if (cfg_in)
+    cfg = *cfg_in;
+  else
+    cox_render_config_default(&cfg);
+  if (!(cfg.max_depth > cfg.min_depth) || !(cfg.min_depth >= 0.0f) || !(cfg.step_scale > 0.0f)) return COX_ERR_INVALID_ARG;  // NaN fails too
+  P->qw = T[0], P->qx = T[1], P->qy = T[2], P->qz = T[3], P->ox = T[4], P->oy = T[5], P->oz = T[6];
+  P->fx = K[0], P->fy = K[1], P->cx = K[2], P->cy = K[3];
+  P->w = w, P->h = h;
+  P->tiles_x = static_cast<u32>((w + kTile - 1) / kTile);
+  P->min_depth = cfg.min_depth, P->max_depth = cfg.max_depth, P->step_scale = cfg.step_scale;
+  P->min_step = cfg.min_step_voxels * L->voxel_size;
+  P->half_voxel = 0.5f * L->voxel_size;
+  P->max_samples = cfg.max_samples;
+  return COX_OK;
+}
+
+void launch_render(const cox_layer* L, const RenderParams& P, float* depth, float* normal, uint8_t* rgba, uint8_t* status, unsigned long long* stats,
+                   hipStream_t s) {
+  const u32 tiles_y = static_cast<u32>((P.h + kTile - 1) / kTile);
+  hipLaunchKernelGGL(k_render, dim3(P.tiles_x * tiles_y), dim3(kRenderThreads), 0, s, layer_view(L), P, depth, normal, reinterpret_cast<u32*>(rgba), status,
+                     stats);
+}
+
+}  // namespace
+
+extern "C" {
+
+void cox_render_config_default(cox_render_config* cfg) {
+  if (!cfg) return;
+  cfg->min_depth = 0.1f;
+  cfg->max_depth = 10.0f;
+  cfg->step_scale = 0.75f;
+  cfg->min_step_voxels = 0.25f;
+  cfg->max_samples = 4096u;
+}
+
+int cox_layer_render(cox_layer_t* L, const float T_G_C[7], int w, int h, const float K[4], const cox_render_config* cfg, float* depth, float* normal,
+                     uint8_t* rgba, uint8_t* status, cox_render_stats* stats) {
+  COX_ENTRY();
+  COX_TRY(device_present());
+  RenderParams P;
+  COX_TRY(check_render_args(L, T_G_C, w, h, K, cfg, &P));
+  COX_HIP(hipSetDevice(L->device));
+  const size_t n = static_cast<size_t>(w) * static_cast<size_t>(h);
+  // one staging allocation: counters | depth | normal | rgba | status
+  const size_t b_cnt = stats ? 4 * sizeof(unsigned long long) : 0, b_d = depth ? 4 * n : 0, b_n = normal ? 12 * n : 0, b_c = rgba ? 4 * n : 0;
+  DevBuf<uint8_t> buf;
+  COX_TRY(buf.alloc(b_cnt + b_d + b_n + b_c + (status ? n : 0)));
+  unsigned long long* d_cnt = stats ? reinterpret_cast<unsigned long long*>(buf.p) : nullptr;
+  float* d_d = depth ? reinterpret_cast<float*>(buf.p + b_cnt) : nullptr;
+  float* d_n = normal ? reinterpret_cast<float*>(buf.p + b_cnt + b_d) : nullptr;
+  uint8_t* d_c = rgba ? buf.p + b_cnt + b_d + b_n : nullptr;
+  uint8_t* d_s = status ? buf.p + b_cnt + b_d + b_n + b_c : nullptr;
+  EventPair ev;
+  if (stats) {
+    COX_HIP(hipEventCreate(&ev.a));
+    COX_HIP(hipEventCreate(&ev.b));
+  }
+  hipStream_t s = nullptr;
+  cox_layer_wait_writes(L, s);  // frames still in flight on the layer
+  if (stats) {
+    COX_HIP(hipMemsetAsync(d_cnt, 0, b_cnt, s));
+    COX_HIP(hipEventRecord(ev.a, s));
+  }
+  launch_render(L, P, d_d, d_n, d_c, d_s, d_cnt, s);
+  COX_HIP(hipGetLastError());
+  if (stats) COX_HIP(hipEventRecord(ev.b, s));
+  unsigned long long cnt[4] = {0, 0, 0, 0};
+  if (stats) COX_HIP(hipMemcpyAsync(cnt, d_cnt, b_cnt, hipMemcpyDeviceToHost, s));
+  if (depth) COX_HIP(hipMemcpyAsync(depth, d_d, b_d, hipMemcpyDeviceToHost, s));
+  if (normal) COX_HIP(hipMemcpyAsync(normal, d_n, b_n, hipMemcpyDeviceToHost, s));
+  if (rgba) COX_HIP(hipMemcpyAsync(rgba, d_c, b_c, hipMemcpyDeviceToHost, s));
+  if (status) COX_HIP(hipMemcpyAsync(status, d_s, n, hipMemcpyDeviceToHost, s));
+  COX_HIP(hipStreamSynchronize(s));
+  if (stats) {
+    float ms = 0.0f;
+    COX_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+    stats->n_hits = cnt[0], stats->n_samples = cnt[1], stats->n_block_skips = cnt[2], stats->n_budget = cnt[3];
+    stats->kernel_ms = static_cast<double>(ms);
+  }
+  return COX_OK;
+}
+
+int cox_layer_render_dev(cox_layer_t* L, const float T_G_C[7], int w, int h, const float K[4], const cox_render_config* cfg, float* depth_dev,
+                         float* normal_dev, uint8_t* rgba_dev, uint8_t* status_dev, void* hip_stream) {
+  COX_ENTRY();
+  COX_TRY(device_present());
+  RenderParams P;
+  COX_TRY(check_render_args(L, T_G_C, w, h, K, cfg, &P));
+  if (reinterpret_cast<uintptr_t>(rgba_dev) & 3u) return COX_ERR_INVALID_ARG;  // a pixel's colour is stored as one word
+  COX_HIP(hipSetDevice(L->device));
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  cox_layer_wait_writes(L, s);
+  launch_render(L, P, depth_dev, normal_dev, rgba_dev, status_dev, nullptr, s);
+  COX_HIP(hipGetLastError());
+  return COX_OK;
+}
+
+}  // extern "C"

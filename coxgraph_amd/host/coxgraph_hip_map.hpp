@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/coxgraph_hip_map.h"
+#include "../../include/coxgraph_hip_render.h"
 #include "coxgraph_hip_submap.hpp"
 
 namespace coxgraph_hip {
@@ -88,6 +89,28 @@ class LayerQuery {
 
   cox_layer_t* layer_;
 };
+
+// What a layer (a TSDF, or an ESDF in TSDF wire layout) looks like from a pose: cox_layer_render into host images.
+struct RenderedView {
+  int width = 0, height = 0;
+  std::vector<float> depth;     // width * height z-depths, row-major; NaN where the ray found no surface
+  std::vector<Point> normal;    // unit gradient of the distance at the hit, pointing into free space; NaN without COX_R_NORMAL
+  std::vector<Color> color;     // colour of the voxel containing the hit; 0 without COX_R_COLOR
+  std::vector<uint8_t> status;  // COX_R_HIT | COX_R_NORMAL | COX_R_COLOR | COX_R_BUDGET
+  cox_render_stats stats;
+};
+// K = {fx, fy, cx, cy}; config NULL: cox_render_config_default
+inline void renderView(cox_layer_t* layer, const Transformation& T_G_C, int width, int height, const float K[4], RenderedView* view,
+                       const cox_render_config* config = nullptr) {
+  const size_t n = (width > 0 && height > 0) ? static_cast<size_t>(width) * static_cast<size_t>(height) : 0;
+  view->width = width, view->height = height;
+  view->depth.resize(n), view->normal.resize(n), view->color.resize(n), view->status.resize(n);
+  float T[7];
+  T_G_C.pack(T);
+  check(cox_layer_render(layer, T, width, height, K, config, view->depth.data(), n ? view->normal[0].data() : nullptr,
+                         reinterpret_cast<uint8_t*>(view->color.data()), view->status.data(), &view->stats),
+        "renderView");
+}
 
 // coxgraph::client::MapServer without the ROS side: the combined TSDF of a submap collection, its ESDF and the traversable cloud
 class MapServer {
