@@ -990,6 +990,83 @@ class MeshLayer:
             eng.fn("meshconn_destroy", None)(h)
         return out
 
+    @staticmethod
+    def connected_mesh(eng, parts, T_per_part=None, proximity_threshold=1e-4):
+        """As connected(), but the welded mesh stays on the GPU: a ConnectedMesh to clean, smooth, cluster and download."""
+        arr = (C.c_void_p * max(1, len(parts)))(*[p.h.value for p in parts])
+        T = None if T_per_part is None else np.ascontiguousarray(np.asarray(T_per_part, np.float32).reshape(len(parts), 7))
+        h = C.c_void_p()
+        eng.check(eng.fn("meshlayer_connected")(arr, _fp(T) if T is not None else None, C.c_uint64(len(parts)), C.c_float(proximity_threshold),
+                                                C.byref(h), None, None), "meshlayer_connected")
+        return ConnectedMesh(eng, h)
+
+
+class ConnectedMesh:
+    """A connected mesh on the GPU (cox_meshconn_t) and its clean-up in place: DESIGN.md section 7h."""
+
+    def __init__(self, eng, h):
+        self.eng, self.h = eng, h
+
+    @classmethod
+    def from_arrays(cls, eng, xyz, triangles, normals=None, rgb=None, device=0):
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        tri = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        col = None if rgb is None else np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+        assert (nrm is None or len(nrm) == len(xyz)) and (col is None or len(col) == len(xyz))
+        h = C.c_void_p()
+        eng.check(eng.fn("meshconn_from_arrays")(C.c_int(device), _fp(xyz), _fp(nrm) if nrm is not None else None, _fp(col) if col is not None else None,
+                                                 _fp(tri), C.c_uint64(len(xyz)), C.c_uint64(len(tri)), C.byref(h)), "meshconn_from_arrays")
+        return cls(eng, h)
+
+    def close(self):
+        if self.h:
+            self.eng.fn("meshconn_destroy", None)(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def size(self):
+        """(vertices, triangles)."""
+        nv, nt = C.c_uint64(), C.c_uint64()
+        self.eng.check(self.eng.fn("meshconn_size")(self.h, C.byref(nv), C.byref(nt)), "meshconn_size")
+        return int(nv.value), int(nt.value)
+
+    def clean(self):
+        """-> (degenerate triangles, duplicate triangles, unreferenced vertices) removed."""
+        r = np.zeros(3, np.uint64)
+        self.eng.check(self.eng.fn("meshconn_clean")(self.h, _fp(r)), "meshconn_clean")
+        return tuple(int(v) for v in r)
+
+    def smooth_taubin(self, iterations=100, lam=0.5, mu=-0.53):
+        """-> HIP-event time of the 2 * iterations half-step launches, in ms."""
+        ms = C.c_double()
+        self.eng.check(self.eng.fn("meshconn_smooth_taubin")(self.h, C.c_int(iterations), C.c_float(lam), C.c_float(mu), C.byref(ms)), "meshconn_smooth_taubin")
+        return float(ms.value)
+
+    def simplify_clustering(self, cell_size):
+        """-> the new (vertices, triangles)."""
+        nv, nt = C.c_uint64(), C.c_uint64()
+        self.eng.check(self.eng.fn("meshconn_simplify_clustering")(self.h, C.c_float(cell_size), C.byref(nv), C.byref(nt)), "meshconn_simplify_clustering")
+        return int(nv.value), int(nt.value)
+
+    def compute_normals(self):
+        self.eng.check(self.eng.fn("meshconn_compute_normals")(self.h), "meshconn_compute_normals")
+
+    def download(self):
+        """dict(xyz, normals, rgb, triangles uint32[nt,3]), as MeshLayer.connected returns."""
+        nv, nt = self.size
+        out = dict(xyz=np.zeros((nv, 3), np.float32), normals=np.zeros((nv, 3), np.float32), rgb=np.zeros((nv, 3), np.uint8),
+                   triangles=np.zeros((nt, 3), np.uint32))
+        self.eng.check(self.eng.fn("meshconn_download")(self.h, *[_fp(out[k]) for k in ("xyz", "normals", "rgb", "triangles")], C.c_uint64(nv), C.c_uint64(nt)),
+                       "meshconn_download")
+        return out
+
 
 # ---- wire-format helpers (voxblox_msgs/Block data words) -----------------------------------------
 def words_to_fields(vox):

@@ -123,6 +123,16 @@ struct cox_meshlayer {
   bool transformed = false;          // cox_meshlayer_transform has moved it out of the layer's frame
 };
 
+// voxblox::Mesh after createConnectedMesh (cox_mesher.hip builds it, cox_meshclean.hip works on it in place)
+struct cox_meshconn {
+  int device = 0;
+  u64 n_vertices = 0, n_triangles = 0;
+  float* pos = nullptr;    // 3 per vertex
+  float* nrm = nullptr;    // 3 per vertex
+  uint8_t* rgb = nullptr;  // 3 per vertex
+  u32* tri = nullptr;      // 3 per triangle
+};
+
 // observation record of a submap (cox_history.hip).  An integrator it is attached to hands it every cloud it fuses:
 // cox_internal_obs_record enqueues the marks on the record's own stream behind the events wait_a / wait_b (either may be null) and
 // records read_done (may be null) once the cloud has been read; nothing is waited for on the host unless settle is set (then the

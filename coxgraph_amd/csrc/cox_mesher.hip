@@ -30,15 +30,6 @@
 
 using namespace cox;
 
-struct cox_meshconn {
-  int device = 0;
-  u64 n_vertices = 0, n_triangles = 0;
-  float* pos = nullptr;
-  float* nrm = nullptr;
-  uint8_t* rgb = nullptr;
-  u32* tri = nullptr;
-};
-
 namespace {
 
 #define COX_TRY(expr)              \
@@ -821,12 +812,12 @@ int cox_meshconn_download(const cox_meshconn_t* C, float* xyz, float* normals, u
   if (!C) return COX_ERR_INVALID_ARG;
   if ((xyz || normals || rgb) && cap_vertices < C->n_vertices) return COX_ERR_BUFFER_TOO_SMALL;
   if (triangles && cap_triangles < C->n_triangles) return COX_ERR_BUFFER_TOO_SMALL;
-  if (C->n_triangles == 0) return COX_OK;
+  if (C->n_vertices == 0 && C->n_triangles == 0) return COX_OK;
   COX_HIP(hipSetDevice(C->device));
-  if (xyz) COX_HIP(hipMemcpy(xyz, C->pos, sizeof(float) * 3 * C->n_vertices, hipMemcpyDeviceToHost));
-  if (normals) COX_HIP(hipMemcpy(normals, C->nrm, sizeof(float) * 3 * C->n_vertices, hipMemcpyDeviceToHost));
-  if (rgb) COX_HIP(hipMemcpy(rgb, C->rgb, 3 * C->n_vertices, hipMemcpyDeviceToHost));
-  if (triangles) COX_HIP(hipMemcpy(triangles, C->tri, sizeof(u32) * 3 * C->n_triangles, hipMemcpyDeviceToHost));
+  if (xyz && C->n_vertices) COX_HIP(hipMemcpy(xyz, C->pos, sizeof(float) * 3 * C->n_vertices, hipMemcpyDeviceToHost));
+  if (normals && C->n_vertices) COX_HIP(hipMemcpy(normals, C->nrm, sizeof(float) * 3 * C->n_vertices, hipMemcpyDeviceToHost));
+  if (rgb && C->n_vertices) COX_HIP(hipMemcpy(rgb, C->rgb, 3 * C->n_vertices, hipMemcpyDeviceToHost));
+  if (triangles && C->n_triangles) COX_HIP(hipMemcpy(triangles, C->tri, sizeof(u32) * 3 * C->n_triangles, hipMemcpyDeviceToHost));
   return COX_OK;
 }
 

@@ -4,8 +4,8 @@
 //                                                               voxblox_msgs/Mesh that recover mode consumes)
 //   ServerVisualizer::getFinalGlobalMesh                        coxgraph/src/server/visualizer/server_visualizer.cpp:20-142 (every
 //                                                               submap meshed, moved by its optimised T_M_S, welded, written as PLY)
-// on top of include/coxgraph_hip_mesh.h: the meshes stay on the submap's GPU until they are downloaded or welded.  Open3D's
-// merge / smooth / simplify steps of the reference's global mesh are not reproduced.
+// on top of include/coxgraph_hip_mesh.h: the meshes stay on the submap's GPU until they are downloaded or welded.  The Open3D
+// steps of the reference's global mesh (merge / dedupe / Taubin smooth / vertex clustering) run on the GPU too: GlobalMeshCleanup.
 #pragma once
 #include <cstdio>
 #include <memory>
@@ -202,6 +202,96 @@ inline void getFinalGlobalMesh(const SubmapCollection& collection, float mesh_mi
     poses.push_back(sm->getPose());
   }
   createConnectedMesh(parts, poses, proximity_threshold, combined_mesh);
+  if (!ply_path.empty() && !outputMeshAsPly(ply_path, *combined_mesh)) throw std::runtime_error("getFinalGlobalMesh: cannot write " + ply_path);
+}
+
+// The Open3D chain of ServerVisualizer::getFinalGlobalMesh (server_visualizer.cpp:67-86) with the reference's constants:
+// MergeCloseVertices(0.06), RemoveDuplicatedVertices / Triangles, FilterSmoothTaubin(100), SimplifyVertexClustering(0.05).
+struct GlobalMeshCleanup {
+  float proximity_threshold = 0.06f;
+  int taubin_iterations = 100;
+  float lambda = 0.5f;
+  float mu = -0.53f;
+  float cluster_size = 0.05f;
+  bool recompute_normals = true;      // smoothing and clustering leave the normals stale
+  bool cleanup_every_submap = false;  // true: the reference's loop, the chain after every appended submap
+};
+
+namespace detail {
+struct MeshConnHandle {  // owns a cox_meshconn_t
+  cox_meshconn_t* h = nullptr;
+  MeshConnHandle() {}
+  ~MeshConnHandle() { cox_meshconn_destroy(h); }
+  MeshConnHandle(const MeshConnHandle&) = delete;
+  MeshConnHandle& operator=(const MeshConnHandle&) = delete;
+};
+inline void downloadConnectedMesh(const cox_meshconn_t* c, ConnectedMesh* out) {
+  uint64_t nv = 0, nt = 0;
+  check(cox_meshconn_size(c, &nv, &nt), "downloadConnectedMesh");
+  out->vertices.assign(3 * nv, 0.0f);
+  out->normals.assign(3 * nv, 0.0f);
+  out->colors.assign(3 * nv, 0);
+  out->indices.assign(3 * nt, 0);
+  check(cox_meshconn_download(c, out->vertices.data(), out->normals.data(), out->colors.data(), out->indices.data(), nv, nt), "downloadConnectedMesh");
+}
+// clean -> smooth -> cluster -> normals, in place on the device
+inline void cleanupConnectedMesh(cox_meshconn_t* c, const GlobalMeshCleanup& cleanup) {
+  check(cox_meshconn_clean(c, nullptr), "cleanupConnectedMesh: clean");
+  check(cox_meshconn_smooth_taubin(c, cleanup.taubin_iterations, cleanup.lambda, cleanup.mu, nullptr), "cleanupConnectedMesh: smooth");
+  check(cox_meshconn_simplify_clustering(c, cleanup.cluster_size, nullptr, nullptr), "cleanupConnectedMesh: cluster");
+  if (cleanup.recompute_normals) check(cox_meshconn_compute_normals(c), "cleanupConnectedMesh: normals");
+}
+}  // namespace detail
+
+// ServerVisualizer::getFinalGlobalMesh with its clean-up: every submap meshed, moved by its pose and welded at
+// cleanup.proximity_threshold; the combined mesh stays on the device through clean, smooth, cluster and normals and is downloaded
+// once.  The reference runs the chain again after every submap it appends, so early submaps are smoothed once per later submap;
+// the default here runs it once over all submaps (cleanup_every_submap = false).  With cleanup_every_submap the loop is the
+// reference's: the cleaned mesh so far and the next submap's welded mesh are concatenated (through the host: one round trip per
+// submap), then the chain runs on the result.
+inline void getFinalGlobalMesh(const SubmapCollection& collection, float mesh_min_weight, const GlobalMeshCleanup& cleanup, ConnectedMesh* combined_mesh,
+                               const std::string& ply_path = std::string()) {
+  SubmapVisuals::Config cfg;
+  cfg.mesh_min_weight = mesh_min_weight;
+  const SubmapVisuals visuals(cfg);
+  std::vector<MeshLayer::Ptr> meshes;
+  std::vector<const cox_meshlayer_t*> parts;
+  std::vector<float> T;
+  for (SubmapID id : collection.getIDs()) {
+    const VoxgraphSubmap::ConstPtr sm = collection.getSubmapConstPtr(id);
+    meshes.emplace_back();
+    visuals.generateSubmapMesh(sm, &meshes.back());
+    parts.push_back(meshes.back()->handle());
+    T.resize(T.size() + 7);
+    sm->getPose().pack(&T[T.size() - 7]);
+  }
+  if (!cleanup.cleanup_every_submap) {
+    detail::MeshConnHandle c;
+    check(cox_meshlayer_connected(parts.data(), T.data(), parts.size(), cleanup.proximity_threshold, &c.h, nullptr, nullptr), "getFinalGlobalMesh");
+    detail::cleanupConnectedMesh(c.h, cleanup);
+    detail::downloadConnectedMesh(c.h, combined_mesh);
+  } else {
+    *combined_mesh = ConnectedMesh();
+    for (size_t k = 0; k < parts.size(); ++k) {
+      ConnectedMesh next;
+      {
+        detail::MeshConnHandle part;
+        check(cox_meshlayer_connected(&parts[k], &T[7 * k], 1, cleanup.proximity_threshold, &part.h, nullptr, nullptr), "getFinalGlobalMesh");
+        detail::downloadConnectedMesh(part.h, &next);
+      }
+      const uint32_t base = static_cast<uint32_t>(combined_mesh->size());
+      combined_mesh->vertices.insert(combined_mesh->vertices.end(), next.vertices.begin(), next.vertices.end());
+      combined_mesh->normals.insert(combined_mesh->normals.end(), next.normals.begin(), next.normals.end());
+      combined_mesh->colors.insert(combined_mesh->colors.end(), next.colors.begin(), next.colors.end());
+      for (uint32_t i : next.indices) combined_mesh->indices.push_back(base + i);
+      detail::MeshConnHandle c;
+      check(cox_meshconn_from_arrays(collection.getConfig().device, combined_mesh->vertices.data(), combined_mesh->normals.data(), combined_mesh->colors.data(),
+                                     combined_mesh->indices.data(), combined_mesh->size(), combined_mesh->indices.size() / 3, &c.h),
+            "getFinalGlobalMesh");
+      detail::cleanupConnectedMesh(c.h, cleanup);
+      detail::downloadConnectedMesh(c.h, combined_mesh);
+    }
+  }
   if (!ply_path.empty() && !outputMeshAsPly(ply_path, *combined_mesh)) throw std::runtime_error("getFinalGlobalMesh: cannot write " + ply_path);
 }
 

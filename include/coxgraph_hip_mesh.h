@@ -68,6 +68,34 @@ int cox_meshconn_size(const cox_meshconn_t* mesh, uint64_t* n_vertices, uint64_t
 int cox_meshconn_download(const cox_meshconn_t* mesh, float* xyz, float* normals, uint8_t* rgb, uint32_t* triangles, uint64_t cap_vertices,
                           uint64_t cap_triangles);
 
+/* ---- clean-up of a connected mesh, in place (what the reference's server leaves to Open3D; rules: DESIGN.md section 7h) ----
+ * Every result is deterministic: the same call on the same mesh gives the same bits.  "Mesh order" = vertex / triangle index order. */
+
+/* A connected mesh from host arrays (xyz 3 floats, normals 3 floats or NULL = zero, rgb 3 bytes or NULL = zero per vertex; 3 uint32
+ * per triangle).  COX_ERR_INDEX_RANGE when a triangle names a vertex >= n_vertices.  Empty input gives an empty mesh. */
+int cox_meshconn_from_arrays(int device, const float* xyz, const float* normals_or_null, const uint8_t* rgb_or_null, const uint32_t* triangles,
+                             uint64_t n_vertices, uint64_t n_triangles, cox_meshconn_t** out);
+/* RemoveDegenerateTriangles + RemoveDuplicatedTriangles + RemoveUnreferencedVertices: (a) a triangle with two equal indices is
+ * dropped; (b) of the triangles with the same canonical form (the rotation with the smallest index first: orientation counts) the
+ * first in mesh order stays, with its own rotation; (c) vertices no surviving triangle names are dropped, the others keep mesh
+ * order, position, normal and colour; triangles are re-indexed.  removed (may be NULL) = the counts of (a), (b), (c). */
+int cox_meshconn_clean(cox_meshconn_t* mesh, uint64_t removed[3]);
+/* FilterSmoothTaubin (Open3D's defaults: lambda 0.5, mu -0.53): per iteration a lambda half-step, then a mu half-step.  A half-step
+ * with factor f moves every vertex at once: p' = p + f * (s / float(|N|) - p), s = the float32 sum of the positions of N = the
+ * vertices that share a triangle edge with it, in ascending index; a vertex without neighbour stays.  Normals and colours are not
+ * touched (cox_meshconn_compute_normals refreshes the normals).  kernel_ms (may be NULL): HIP-event time of the 2 * iterations
+ * launches.  COX_ERR_INVALID_ARG for iterations < 0 or a factor that is not finite. */
+int cox_meshconn_smooth_taubin(cox_meshconn_t* mesh, int iterations, float lambda, float mu, double* kernel_ms);
+/* SimplifyVertexClustering with average contraction: per axis origin = min(p) - 0.5f * cell_size and
+ * cell = int(floorf((p - origin) / cell_size)) in float32; one vertex per occupied cell, in ascending (z, y, x) cell order;
+ * position = float32 sum of the members in ascending index / float(count), colour = rounded integer mean, normal = normalized
+ * sum; triangles re-indexed, then cleaned as cox_meshconn_clean does.  COX_ERR_INVALID_ARG unless cell_size is finite and > 0;
+ * COX_ERR_INDEX_RANGE when an axis spans 2^21 cells or more.  n_vertices / n_triangles (may be NULL): the new sizes. */
+int cox_meshconn_simplify_clustering(cox_meshconn_t* mesh, float cell_size, uint64_t* n_vertices, uint64_t* n_triangles);
+/* ComputeVertexNormals: normalized sum, over the triangles of a vertex in ascending index, of cross(p1 - p0, p2 - p0) (area
+ * weighted); (0, 0, 0) for a vertex without triangle. */
+int cox_meshconn_compute_normals(cox_meshconn_t* mesh);
+
 #ifdef __cplusplus
 }
 #endif
