@@ -1068,6 +1068,158 @@ class ConnectedMesh:
         return out
 
 
+# ---- scan-to-map registration (include/coxgraph_hip_track.h) ---------------------------------------
+TRACK_STATUS = {0: "converged", 1: "max_iterations", 2: "lost", 3: "degenerate"}
+TRACK_CONSIDERED, TRACK_USED = 1, 2  # status bits of Tracker.evaluate
+TRACK_GRID_PASS = 65536              # COX_TRACK_GRID_PASS: candidates one pass of the kernel's grid covers
+
+
+class TrackConfig(C.Structure):
+    """cox_track_config."""
+    _fields_ = [("dof", C.c_int32), ("max_iterations", C.c_uint32), ("stride", C.c_uint32), ("min_points", C.c_uint32),
+                ("max_abs_distance", C.c_float), ("reserved", C.c_float), ("huber_delta", C.c_double), ("damping", C.c_double),
+                ("translation_tolerance", C.c_double), ("rotation_tolerance", C.c_double), ("min_inlier_ratio", C.c_double)]
+
+
+class TrackResult(C.Structure):
+    """cox_track_result."""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_uint32), ("first_n_used", C.c_uint64), ("first_n_considered", C.c_uint64),
+                ("last_n_used", C.c_uint64), ("last_n_considered", C.c_uint64), ("first_cost", C.c_double), ("last_cost", C.c_double),
+                ("last_step_translation", C.c_double), ("last_step_rotation", C.c_double), ("T_G_C", C.c_double * 7), ("kernel_ms", C.c_double)]
+
+    def asdict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "T_G_C"}
+        d["T"] = np.array(self.T_G_C[:], np.float64)
+        d["status_name"] = TRACK_STATUS.get(self.status, str(self.status))
+        return d
+
+
+def track_config(eng, **cfg):
+    c = TrackConfig()
+    eng.fn("track_config_default", None)(C.byref(c))
+    for k, v in cfg.items():
+        if not hasattr(c, k):
+            raise AttributeError(k)
+        setattr(c, k, v)
+    return c
+
+
+class Tracker:
+    """Scan-to-map registration against a layer (cox_track_t): cfg are fields of cox_track_config."""
+
+    def __init__(self, eng, layer, **cfg):
+        self.eng, self.layer = eng, layer  # (keeps the layer alive)
+        self.cfg = track_config(eng, **cfg)
+        self.h = C.c_void_p()
+        eng.check(eng.fn("track_create")(layer.h, C.byref(self.cfg), C.byref(self.h)), "track_create")
+
+    def close(self):
+        if self.h:
+            self.eng.fn("track_destroy", None)(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _ptr(t):
+        if t is None:
+            return None
+        return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+
+    @staticmethod
+    def _pose(T):
+        T = np.ascontiguousarray(T, np.float32)
+        assert T.shape == (7,)
+        return T
+
+    def _result(self, res, T_refined):
+        out = res.asdict()
+        out["T_refined"] = T_refined
+        return out
+
+    def evaluate(self, T_G_C, xyz):
+        """The per-point values of one iteration (cox_track_evaluate_dev) for host points [n,3]: dict(status uint8[n] of
+        TRACK_CONSIDERED | TRACK_USED, pG[n,3], d[n], g[n,3]); NaN where the matching bit is clear."""
+        import torch
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        dx = torch.from_numpy(xyz).cuda()
+        vals = torch.empty((n, 7), dtype=torch.float32, device="cuda")
+        st = torch.empty(n, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        self.eng.check(self.eng.fn("track_evaluate_dev")(self.h, _fp(self._pose(T_G_C)), self._ptr(dx), C.c_uint64(n), self._ptr(vals), self._ptr(st)),
+                       "track_evaluate_dev")
+        v = vals.cpu().numpy()
+        return dict(status=st.cpu().numpy(), pG=v[:, 0:3].copy(), d=v[:, 3].copy(), g=v[:, 4:7].copy())
+
+    def _normal_eq_out(self, call, what):
+        H, b, cost, counts = np.zeros(36, np.float64), np.zeros(6, np.float64), C.c_double(), (C.c_uint64 * 2)()
+        self.eng.check(call(_fp(H), _fp(b), C.byref(cost), counts), what)
+        dof = self.cfg.dof
+        return dict(H=H.reshape(6, 6)[:dof, :dof].copy(), b=b[:dof].copy(), cost=cost.value, n_used=int(counts[0]), n_considered=int(counts[1]))
+
+    def normal_eq(self, T_G_C, xyz, n=None):
+        """One evaluation of the normal equations, no update (cox_track_normal_eq_dev): xyz a torch tensor on the layer's GPU, a raw
+        device pointer (then n is required) or a host array.  dict(H[dof,dof], b[dof], cost, n_used, n_considered)."""
+        xyz, n = self._dev_points(xyz, n)
+        T = self._pose(T_G_C)
+        f = self.eng.fn("track_normal_eq_dev")
+        return self._normal_eq_out(lambda *o: f(self.h, _fp(T), self._ptr(xyz), C.c_uint64(n), *o), "track_normal_eq_dev")
+
+    def normal_eq_depth_dev(self, T_G_C, depth, w, h, K=None):
+        """normal_eq on a depth image on the device (cox_track_normal_eq_depth_dev)."""
+        T, K = self._pose(T_G_C), self._intrinsics(w, h, K)
+        f = self.eng.fn("track_normal_eq_depth_dev")
+        return self._normal_eq_out(lambda *o: f(self.h, _fp(T), self._ptr(depth), C.c_int(w), C.c_int(h), _fp(K), *o), "track_normal_eq_depth_dev")
+
+    @staticmethod
+    def _intrinsics(w, h, K):
+        if K is None:
+            from . import synth
+            K = synth.INTRINSICS[(w, h)]
+        K = np.ascontiguousarray(K, np.float32)
+        assert K.shape == (4,)
+        return K
+
+    def _dev_points(self, xyz, n):
+        if isinstance(xyz, np.ndarray):
+            import torch
+            xyz = torch.from_numpy(np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)).cuda()
+            torch.cuda.synchronize()
+        if n is None:
+            n = xyz.numel() // 3
+        return xyz, n
+
+    def refine(self, T_prior, xyz):
+        """cox_track_refine with host points [n,3]: the fields of cox_track_result as a dict (T float64[7], status_name, ...)
+        plus T_refined float32[7]."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        res, Tr = TrackResult(), np.zeros(7, np.float32)
+        self.eng.check(self.eng.fn("track_refine")(self.h, _fp(self._pose(T_prior)), _fp(xyz), C.c_uint64(len(xyz)), _fp(Tr), C.byref(res)), "track_refine")
+        return self._result(res, Tr)
+
+    def refine_dev(self, T_prior, xyz, n=None):
+        """cox_track_refine_dev: xyz a torch tensor on the layer's GPU or a raw device pointer (then n is required), complete
+        when the call is made."""
+        if n is None:
+            n = xyz.numel() // 3
+        res, Tr = TrackResult(), np.zeros(7, np.float32)
+        self.eng.check(self.eng.fn("track_refine_dev")(self.h, _fp(self._pose(T_prior)), self._ptr(xyz), C.c_uint64(n), _fp(Tr), C.byref(res)), "track_refine_dev")
+        return self._result(res, Tr)
+
+    def refine_depth_dev(self, T_prior, depth, w, h, K=None):
+        """cox_track_refine_depth_dev: depth a torch tensor [h,w] on the layer's GPU or a raw device pointer, in the layout of
+        Integrator.integrate_depth_dev and Layer.render_dev; K None: synth.INTRINSICS[(w, h)]."""
+        res, Tr = TrackResult(), np.zeros(7, np.float32)
+        self.eng.check(self.eng.fn("track_refine_depth_dev")(self.h, _fp(self._pose(T_prior)), self._ptr(depth), C.c_int(w), C.c_int(h),
+                                                             _fp(self._intrinsics(w, h, K)), _fp(Tr), C.byref(res)), "track_refine_depth_dev")
+        return self._result(res, Tr)
+
+
 # ---- wire-format helpers (voxblox_msgs/Block data words) -----------------------------------------
 def words_to_fields(vox):
     """uint32[...,3] wire words -> (distance f32, weight f32, rgba u8[...,4])."""
