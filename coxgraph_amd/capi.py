@@ -303,6 +303,15 @@ class Layer:
         self.eng.check(self.eng.fn("layer_render_dev")(self.h, _fp(T), C.c_int(w), C.c_int(h), _fp(K), C.byref(c), ptr(depth), ptr(normal), ptr(rgba),
                                                        ptr(status), C.c_void_p(s or 0)), "layer_render_dev")
 
+    # ---- view gain (include/coxgraph_hip_gain.h) ----
+    def view_gain(self, poses, **cfg):
+        """ViewGain(self, **cfg).evaluate(poses) with a throw-away evaluator: the gain records of candidate poses [n,7]."""
+        vg = ViewGain(self.eng, self, **cfg)
+        try:
+            return vg.evaluate(poses)
+        finally:
+            vg.close()
+
     def free_points(self, min_distance):
         """createFreePointcloudFromEsdfLayer: (xyz float32[n,3] voxel centres, intensity float32[n] distances), blocks in download
         order, voxels in linear index order."""
@@ -1218,6 +1227,108 @@ class Tracker:
         self.eng.check(self.eng.fn("track_refine_depth_dev")(self.h, _fp(self._pose(T_prior)), self._ptr(depth), C.c_int(w), C.c_int(h),
                                                              _fp(self._intrinsics(w, h, K)), _fp(Tr), C.byref(res)), "track_refine_depth_dev")
         return self._result(res, Tr)
+
+
+# ---- view gain for exploration (include/coxgraph_hip_gain.h) ---------------------------------------
+VG_FREE, VG_OCCUPIED, VG_UNKNOWN, VG_FRONTIER = 0, 1, 2, 3  # class of a visible voxel (ViewGain.visible)
+VG_COUNTS = ("n_visible", "n_free", "n_occupied", "n_surface_counted", "n_unknown", "n_frontier")
+
+
+class ViewGainConfig(C.Structure):
+    """cox_viewgain_config."""
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("K", C.c_float * 4), ("min_range", C.c_float), ("ray_length", C.c_float), ("ray_step", C.c_float),
+                ("min_weight", C.c_float), ("surface_distance", C.c_float), ("frontier_voxel_weight", C.c_float), ("new_voxel_weight", C.c_float),
+                ("min_impact_factor", C.c_float), ("ray_angle_x", C.c_float), ("ray_angle_y", C.c_float), ("accurate_frontiers", C.c_int32),
+                ("surface_frontiers", C.c_int32), ("use_box", C.c_int32), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3),
+                ("workspace_bytes", C.c_uint64)]
+
+
+class ViewGainRecord(C.Structure):
+    """cox_view_gain."""
+    _fields_ = [("gain", C.c_double), ("surface_gain", C.c_double), ("surface_gain_q32", C.c_uint64)] + [(n, C.c_uint32) for n in VG_COUNTS]
+
+
+VIEW_GAIN_DTYPE = np.dtype([("gain", np.float64), ("surface_gain", np.float64), ("surface_gain_q32", np.uint64)] + [(n, np.uint32) for n in VG_COUNTS])
+assert VIEW_GAIN_DTYPE.itemsize == C.sizeof(ViewGainRecord) == 48
+
+
+class ViewGainStats(C.Structure):
+    _fields_ = [("n_samples", C.c_uint64), ("n_chunks", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+def viewgain_config(eng, **cfg):
+    """cox_viewgain_config_default with overrides; K, box_min and box_max take sequences."""
+    c = ViewGainConfig()
+    eng.fn("viewgain_config_default", None)(C.byref(c))
+    for k, v in cfg.items():
+        if not hasattr(c, k):
+            raise AttributeError(k)
+        if k in ("K", "box_min", "box_max"):
+            v = type(getattr(c, k))(*[float(x) for x in v])
+        setattr(c, k, v)
+    return c
+
+
+class ViewGain:
+    """Scores candidate views against a layer (cox_viewgain_t): cfg are fields of cox_viewgain_config."""
+
+    def __init__(self, eng, layer, **cfg):
+        self.eng, self.layer = eng, layer  # (keeps the layer alive)
+        self.cfg = viewgain_config(eng, **cfg)
+        self.h = C.c_void_p()
+        eng.check(eng.fn("viewgain_create")(layer.h, C.byref(self.cfg), C.byref(self.h)), "viewgain_create")
+
+    def close(self):
+        if self.h:
+            self.eng.fn("viewgain_destroy", None)(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def view_bytes(self):
+        """Workspace bytes one view takes (cox_viewgain_view_bytes)."""
+        return int(self.eng.fn("viewgain_view_bytes", C.c_uint64)(self.h))
+
+    def evaluate(self, poses):
+        """cox_viewgain_evaluate for host poses [n,7] (qw qx qy qz tx ty tz): dict of numpy arrays over the views -- gain,
+        surface_gain, surface_gain_q32 and the counts of cox_view_gain -- plus stats (n_samples, n_chunks, kernel_ms)."""
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 7)
+        n = len(poses)
+        rec = np.zeros(n, VIEW_GAIN_DTYPE)
+        st = ViewGainStats()
+        self.eng.check(self.eng.fn("viewgain_evaluate")(self.h, _fp(poses), C.c_uint64(n), _fp(rec), C.byref(st)), "viewgain_evaluate")
+        out = {k: rec[k].copy() for k in VIEW_GAIN_DTYPE.names}
+        out["stats"] = dict(n_samples=int(st.n_samples), n_chunks=int(st.n_chunks), kernel_ms=float(st.kernel_ms))
+        return out
+
+    def evaluate_dev(self, poses_dev, out_dev, stream=None, n=None):
+        """cox_viewgain_evaluate_dev: poses_dev a float32 torch tensor [n,7] on the layer's GPU (or a raw device pointer; then n is
+        required), out_dev a tensor of n * 48 bytes (view it with VIEW_GAIN_DTYPE once it is on the host) or a raw pointer; enqueued
+        on `stream` (a torch stream, a raw hipStream_t or None = the null stream), not waited for."""
+        def ptr(t):
+            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        if n is None:
+            n = poses_dev.numel() // 7
+        s = getattr(stream, "cuda_stream", stream)
+        self.eng.check(self.eng.fn("viewgain_evaluate_dev")(self.h, ptr(poses_dev), C.c_uint64(n), ptr(out_dev), C.c_void_p(s or 0)), "viewgain_evaluate_dev")
+
+    def visible(self, pose):
+        """The visible set of one view (cox_viewgain_visible): dict(voxel_xyz int32[n,3] global voxel indices, cls uint8[n] of
+        VG_FREE | VG_OCCUPIED | VG_UNKNOWN | VG_FRONTIER, value float32[n]) in ascending (z, y, x) order."""
+        pose = np.ascontiguousarray(pose, np.float32)
+        assert pose.shape == (7,)
+        f = self.eng.fn("viewgain_visible")
+        n = C.c_uint64()
+        self.eng.check(f(self.h, _fp(pose), C.c_uint64(0), None, None, None, C.byref(n)), "viewgain_visible(query)")
+        k = int(n.value)
+        out = dict(voxel_xyz=np.zeros((k, 3), np.int32), cls=np.zeros(k, np.uint8), value=np.zeros(k, np.float32))
+        if k:
+            self.eng.check(f(self.h, _fp(pose), C.c_uint64(k), _fp(out["voxel_xyz"]), _fp(out["cls"]), _fp(out["value"]), C.byref(n)), "viewgain_visible")
+        return out
 
 
 # ---- wire-format helpers (voxblox_msgs/Block data words) -----------------------------------------
