@@ -312,6 +312,15 @@ class Layer:
         finally:
             vg.close()
 
+    # ---- collision checks (include/coxgraph_hip_collide.h) ----
+    def check_segments(self, a, b, **cfg):
+        """CollisionChecker(self, **cfg).segments(a, b) with a throw-away checker: one record per straight segment a -> b."""
+        cc = CollisionChecker(self.eng, self, **cfg)
+        try:
+            return cc.segments(a, b)
+        finally:
+            cc.close()
+
     def free_points(self, min_distance):
         """createFreePointcloudFromEsdfLayer: (xyz float32[n,3] voxel centres, intensity float32[n] distances), blocks in download
         order, voxels in linear index order."""
@@ -1329,6 +1338,190 @@ class ViewGain:
         if k:
             self.eng.check(f(self.h, _fp(pose), C.c_uint64(k), _fp(out["voxel_xyz"]), _fp(out["cls"]), _fp(out["value"]), C.byref(n)), "viewgain_visible")
         return out
+
+
+# ---- collision checks for a planner (include/coxgraph_hip_collide.h) --------------------------------
+C_TRAVERSABLE, C_OBSERVED, C_DISTANCE, C_CLEARED, C_INVALID = 1, 2, 4, 8, 16  # state of a sample (CollisionChecker.points)
+SEG_FEASIBLE, SEG_GOAL, SEG_CLAMPED, SEG_TOO_LONG, SEG_INVALID = 1, 2, 4, 8, 16  # flags of a record
+TREE_KEEP, TREE_INVALID = 1, 2  # keep[] of a tree
+
+
+class CollideConfig(C.Structure):
+    """cox_collide_config."""
+    _fields_ = [("collision_radius", C.c_float), ("collision_optimistic", C.c_int32), ("clearing_radius", C.c_float), ("clearing_centre", C.c_float * 3),
+                ("sample_spacing", C.c_float), ("max_samples", C.c_uint32), ("max_extension_range", C.c_float), ("crop", C.c_int32),
+                ("crop_margin", C.c_float), ("crop_min_length", C.c_float)]
+
+
+class CollideStats(C.Structure):
+    _fields_ = [("n_samples_evaluated", C.c_uint64), ("n_samples_skipped", C.c_uint64), ("n_launches", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+COLLIDE_RECORD_DTYPE = np.dtype([("n_samples", np.uint32), ("first_blocked", np.uint32), ("flags", np.uint32), ("free_length", np.float32),
+                                 ("goal", np.float32, 3), ("pad", np.uint32)])
+assert COLLIDE_RECORD_DTYPE.itemsize == 32
+
+
+def collide_config(eng, **cfg):
+    """cox_collide_config_default with overrides; clearing_centre takes a sequence."""
+    c = CollideConfig()
+    eng.fn("collide_config_default", None)(C.byref(c))
+    for k, v in cfg.items():
+        if not hasattr(c, k):
+            raise AttributeError(k)
+        if k == "clearing_centre":
+            v = (C.c_float * 3)(*[float(x) for x in v])
+        setattr(c, k, v)
+    return c
+
+
+class CollisionChecker:
+    """Checks planner paths against a layer (cox_collide_t): cfg are fields of cox_collide_config, group_size 32 or 64."""
+
+    def __init__(self, eng, layer, group_size=None, **cfg):
+        self.eng, self.layer = eng, layer  # (keeps the layer alive)
+        self.cfg = collide_config(eng, **cfg)
+        self.h = C.c_void_p()
+        eng.check(eng.fn("collide_create")(layer.h, C.byref(self.cfg), C.byref(self.h)), "collide_create")
+        if group_size is not None:
+            self.set_group_size(group_size)
+
+    def close(self):
+        if self.h:
+            self.eng.fn("collide_destroy", None)(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_clearing_centre(self, centre):
+        c = np.ascontiguousarray(centre, np.float32)
+        assert c.shape == (3,)
+        self.eng.check(self.eng.fn("collide_set_clearing_centre")(self.h, _fp(c)), "collide_set_clearing_centre")
+
+    def set_group_size(self, lanes):
+        self.eng.check(self.eng.fn("collide_set_group_size")(self.h, C.c_int(lanes)), "collide_set_group_size")
+
+    def set_profiling(self, on=True):
+        self.eng.check(self.eng.fn("collide_set_profiling")(self.h, C.c_int(int(on))), "collide_set_profiling")
+
+    def stats(self, reset=False):
+        st = CollideStats()
+        self.eng.check(self.eng.fn("collide_stats")(self.h, C.byref(st), C.c_int(int(reset))), "collide_stats")
+        return dict(n_samples_evaluated=int(st.n_samples_evaluated), n_samples_skipped=int(st.n_samples_skipped), n_launches=int(st.n_launches),
+                    kernel_ms=float(st.kernel_ms))
+
+    @staticmethod
+    def _ptr(t):
+        if t is None:
+            return None
+        return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+
+    @staticmethod
+    def _stream(stream):
+        return C.c_void_p(getattr(stream, "cuda_stream", stream) or 0)
+
+    @staticmethod
+    def _records(rec):
+        return {k: rec[k].copy() for k in COLLIDE_RECORD_DTYPE.names if k != "pad"}
+
+    def points(self, xyz):
+        """cox_collide_points at float32 points [n,3]: dict(state[n] uint8 of C_*, distance[n], NaN without C_DISTANCE)."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        out = dict(state=np.zeros(n, np.uint8), distance=np.full(n, np.nan, np.float32))
+        self.eng.check(self.eng.fn("collide_points")(self.h, _fp(xyz), C.c_uint64(n), _fp(out["state"]), _fp(out["distance"])), "collide_points")
+        return out
+
+    def points_dev(self, xyz, state=None, distance=None, n=None, stream=None):
+        """cox_collide_points_dev: torch tensors on the layer's GPU or raw device pointers (ints; then n is required), enqueued on
+        `stream` (a torch stream, a raw hipStream_t or None = the null stream), not waited for."""
+        if n is None:
+            n = xyz.numel() // 3
+        self.eng.check(self.eng.fn("collide_points_dev")(self.h, self._ptr(xyz), C.c_uint64(n), self._ptr(state), self._ptr(distance),
+                                                         self._stream(stream)), "collide_points_dev")
+
+    def segments(self, a, b):
+        """cox_collide_segments for straight segments a[n,3] -> b[n,3]: dict of numpy arrays over the segments -- n_samples,
+        first_blocked, flags (SEG_*), free_length, goal[n,3]."""
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(b, np.float32).reshape(-1, 3)
+        assert a.shape == b.shape
+        rec = np.zeros(len(a), COLLIDE_RECORD_DTYPE)
+        rec["free_length"] = rec["goal"] = np.nan
+        self.eng.check(self.eng.fn("collide_segments")(self.h, _fp(a), _fp(b), C.c_uint64(len(a)), _fp(rec)), "collide_segments")
+        return self._records(rec)
+
+    def segments_dev(self, a, b, out, n=None, stream=None):
+        """cox_collide_segments_dev: out a tensor of n * 32 bytes (view it with COLLIDE_RECORD_DTYPE on the host) or a raw pointer."""
+        if n is None:
+            n = a.numel() // 3
+        self.eng.check(self.eng.fn("collide_segments_dev")(self.h, self._ptr(a), self._ptr(b), C.c_uint64(n), self._ptr(out), self._stream(stream)),
+                       "collide_segments_dev")
+
+    @staticmethod
+    def _csr(offsets, xyz):
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        assert offsets.ndim == 1 and len(offsets) >= 1
+        return offsets, xyz
+
+    def trajectories(self, offsets, xyz):
+        """cox_collide_trajectories: trajectory t is xyz[offsets[t]:offsets[t + 1]]; dict as segments() (free_length and goal NaN)."""
+        offsets, xyz = self._csr(offsets, xyz)
+        rec = np.zeros(len(offsets) - 1, COLLIDE_RECORD_DTYPE)
+        rec["free_length"] = rec["goal"] = np.nan
+        self.eng.check(self.eng.fn("collide_trajectories")(self.h, _fp(offsets), C.c_uint64(len(offsets) - 1), _fp(xyz), C.c_uint64(len(xyz)),
+                                                           _fp(rec)), "collide_trajectories")
+        return self._records(rec)
+
+    def trajectories_dev(self, offsets, n_traj, xyz, n_points, out, stream=None):
+        self.eng.check(self.eng.fn("collide_trajectories_dev")(self.h, self._ptr(offsets), C.c_uint64(n_traj), self._ptr(xyz), C.c_uint64(n_points),
+                                                               self._ptr(out), self._stream(stream)), "collide_trajectories_dev")
+
+    def prune_dev(self, parent, feasible, keep, n=None, feasible_stride=1, stream=None):
+        """cox_collide_prune_dev: parent int32[n], feasible bytes (bit 0, feasible_stride bytes apart), keep uint8[n] of TREE_*."""
+        if n is None:
+            n = parent.numel()
+        self.eng.check(self.eng.fn("collide_prune_dev")(self.h, self._ptr(parent), self._ptr(feasible), C.c_uint64(feasible_stride), C.c_uint64(n),
+                                                        self._ptr(keep), self._stream(stream)), "collide_prune_dev")
+
+    def prune(self, parent, feasible):
+        """keep uint8[n] of a tree given on the host (staged through torch; the rule runs in cox_collide_prune_dev)."""
+        import torch
+        parent = np.ascontiguousarray(parent, np.int32)
+        feasible = np.ascontiguousarray(feasible, np.uint8)
+        assert parent.shape == feasible.shape and parent.ndim == 1
+        if len(parent) == 0:
+            return np.zeros(0, np.uint8)
+        p, f = torch.from_numpy(parent).cuda(), torch.from_numpy(feasible).cuda()
+        keep = torch.zeros(len(parent), dtype=torch.uint8, device="cuda")
+        s = torch.cuda.current_stream()
+        self.prune_dev(p, f, keep, stream=s)
+        s.synchronize()
+        return keep.cpu().numpy()
+
+    def tree(self, offsets, parent, xyz):
+        """cox_collide_tree: node i owns trajectory i; dict as trajectories() plus keep uint8[n] of TREE_*."""
+        offsets, xyz = self._csr(offsets, xyz)
+        parent = np.ascontiguousarray(parent, np.int32)
+        n = len(offsets) - 1
+        assert parent.shape == (n,)
+        rec = np.zeros(n, COLLIDE_RECORD_DTYPE)
+        rec["free_length"] = rec["goal"] = np.nan
+        keep = np.zeros(n, np.uint8)
+        self.eng.check(self.eng.fn("collide_tree")(self.h, _fp(offsets), _fp(parent), C.c_uint64(n), _fp(xyz), C.c_uint64(len(xyz)), _fp(rec),
+                                                   _fp(keep)), "collide_tree")
+        out = self._records(rec)
+        out["keep"] = keep
+        return out
+
+    def tree_dev(self, offsets, parent, n_nodes, xyz, n_points, out, keep, stream=None):
+        self.eng.check(self.eng.fn("collide_tree_dev")(self.h, self._ptr(offsets), self._ptr(parent), C.c_uint64(n_nodes), self._ptr(xyz),
+                                                       C.c_uint64(n_points), self._ptr(out), self._ptr(keep), self._stream(stream)), "collide_tree_dev")
 
 
 # ---- wire-format helpers (voxblox_msgs/Block data words) -----------------------------------------

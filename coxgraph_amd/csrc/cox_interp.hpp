@@ -1,5 +1,5 @@
-// voxblox Interpolator<TsdfVoxel>::getVoxelsAndQVector on the GPU, shared by the registration cost (cox_reg.hip) and the map
-// queries (cox_query.hip).  The arithmetic is oracle/cox_oracle.hpp's getVoxelsAndQVector + interpMember, expression by
+// voxblox Interpolator<TsdfVoxel>::getVoxelsAndQVector on the GPU, shared by the registration cost (cox_reg.hip), the map
+// queries (cox_query.hip) and the collision checks (cox_collide.hip).  The arithmetic is oracle/cox_oracle.hpp's getVoxelsAndQVector + interpMember, expression by
 // expression, so both kernels reproduce the checker bit for bit.
 #pragma once
 #include "cox_device.hpp"
@@ -118,6 +118,83 @@ __device__ __forceinline__ float interp_member(const float off[3], const float d
 #pragma unroll
   for (int i = 0; i < 8; ++i) v += q[i] * md[i];
   return v;
+}
+
+// ---- point samples on a layer, shared by the map queries (cox_query.hip) and the collision checks (cox_collide.hip) ----------
+// pool indices of the up to 2 x 2 x 2 blocks around a query, resolved once; anything else is looked up in the hash table
+struct BlockCache {
+  const LayerView& L;
+  int lo[3];
+  u32 pool[8];  // (x - lo.x) << 2 | (y - lo.y) << 1 | (z - lo.z); kInvalid when missing
+  u32 have;     // bit c: pool[c] was resolved
+  __device__ __forceinline__ u32 operator()(int x, int y, int z) const {
+    const u32 dx = static_cast<u32>(x - lo[0]), dy = static_cast<u32>(y - lo[1]), dz = static_cast<u32>(z - lo[2]);
+    if (dx <= 1u && dy <= 1u && dz <= 1u) {
+      const u32 sel = (dx << 2) | (dy << 1) | dz;
+      if ((have >> sel) & 1u) {
+        u32 r = pool[0];
+#pragma unroll
+        for (u32 c = 1; c < 8; ++c) r = sel == c ? pool[c] : r;  // no dynamic register indexing (it would go to scratch)
+        return r;
+      }
+    }
+    return HtPool{L}(x, y, z);
+  }
+};
+
+// Resolves into bc the blocks of voxels g - R .. g + R around the voxel g that contains p (sc = p * block_size_inv, in index
+// range): only the blocks that range touches, so one lookup for a point deep inside a block.  b[] gets the block of p.
+template <int R>
+__device__ __forceinline__ void block_cache_fill(const LayerView& L, const float p[3], const float sc[3], BlockCache& bc, int b[3]) {
+  int span[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    b[k] = grid_index(sc[k]);
+    const int v = grid_index((p[k] - static_cast<float>(b[k]) * L.block_size) * L.voxel_size_inv);
+    const int g = b[k] * 16 + (v > 15 ? 15 : (v < 0 ? 0 : v));
+    bc.lo[k] = (g - R) >> 4;
+    span[k] = ((g + R) >> 4) - bc.lo[k];
+  }
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const int mx = (c >> 2) & 1, my = (c >> 1) & 1, mz = c & 1;
+    if (mx <= span[0] && my <= span[1] && mz <= span[2]) {
+      bc.pool[c] = HtPool{L}(bc.lo[0] + mx, bc.lo[1] + my, bc.lo[2] + mz);
+      bc.have |= 1u << c;
+    }
+  }
+}
+
+// Interpolator::getInterpDistance (and getInterpWeight when want_w) at s: false when the cell is incomplete or invalid
+__device__ __forceinline__ bool tri_sample(const LayerView& L, const BlockCache& bc, const float s[3], float* d, float* w, bool want_w) {
+  int b[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) b[k] = grid_index(s[k] * L.block_size_inv);
+  if (bc(b[0], b[1], b[2]) == kInvalid) return false;  // getBlockPtrByCoordinates(pos)
+  float dd[8], ww[8], off[3];
+  if (!interp_cell(L, s, b, bc, dd, ww, off)) return false;
+  *d = interp_member(off, dd);
+  if (want_w) *w = interp_member(off, ww);
+  return true;
+}
+
+// Block::getVoxelByCoordinates: the containing block, the grid index clamped into it; valid when weight > 0
+__device__ __forceinline__ bool nearest_sample(const LayerView& L, const BlockCache& bc, const float s[3], float* d, float* w) {
+  int b[3], v[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) b[k] = grid_index(s[k] * L.block_size_inv);
+  const u32 pool = bc(b[0], b[1], b[2]);
+  if (pool == kInvalid) return false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float rel = s[k] - static_cast<float>(b[k]) * L.block_size;
+    const int g = grid_index(rel * L.voxel_size_inv);
+    v[k] = g > 15 ? 15 : (g < 0 ? 0 : g);
+  }
+  const u32* vox = L.voxels + (static_cast<size_t>(pool) * kVoxelsPerBlock + static_cast<u32>(v[0] + 16 * (v[1] + 16 * v[2]))) * kWordsPerVoxel;
+  *d = __uint_as_float(vox[0]);
+  *w = __uint_as_float(vox[1]);
+  return *w > 0.0f;
 }
 
 }  // namespace cox

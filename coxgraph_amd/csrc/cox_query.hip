@@ -67,59 +67,6 @@ LayerView layer_view(const cox_layer* L) {
 // ---- the query kernel ------------------------------------------------------------------------------------------------------
 constexpr int kQueryThreads = 256;
 
-// pool indices of the up to 2 x 2 x 2 blocks around a query, resolved once; anything else is looked up in the hash table
-struct BlockCache {
-  const LayerView& L;
-  int lo[3];
-  u32 pool[8];  // (x - lo.x) << 2 | (y - lo.y) << 1 | (z - lo.z); kInvalid when missing
-  u32 have;     // bit c: pool[c] was resolved
-  __device__ __forceinline__ u32 operator()(int x, int y, int z) const {
-    const u32 dx = static_cast<u32>(x - lo[0]), dy = static_cast<u32>(y - lo[1]), dz = static_cast<u32>(z - lo[2]);
-    if (dx <= 1u && dy <= 1u && dz <= 1u) {
-      const u32 sel = (dx << 2) | (dy << 1) | dz;
-      if ((have >> sel) & 1u) {
-        u32 r = pool[0];
-#pragma unroll
-        for (u32 c = 1; c < 8; ++c) r = sel == c ? pool[c] : r;  // no dynamic register indexing (it would go to scratch)
-        return r;
-      }
-    }
-    return HtPool{L}(x, y, z);
-  }
-};
-
-// Interpolator::getInterpDistance (and getInterpWeight when want_w) at s: false when the cell is incomplete or invalid
-__device__ __forceinline__ bool tri_sample(const LayerView& L, const BlockCache& bc, const float s[3], float* d, float* w, bool want_w) {
-  int b[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) b[k] = grid_index(s[k] * L.block_size_inv);
-  if (bc(b[0], b[1], b[2]) == kInvalid) return false;  // getBlockPtrByCoordinates(pos)
-  float dd[8], ww[8], off[3];
-  if (!interp_cell(L, s, b, bc, dd, ww, off)) return false;
-  *d = interp_member(off, dd);
-  if (want_w) *w = interp_member(off, ww);
-  return true;
-}
-
-// Block::getVoxelByCoordinates: the containing block, the grid index clamped into it; valid when weight > 0
-__device__ __forceinline__ bool nearest_sample(const LayerView& L, const BlockCache& bc, const float s[3], float* d, float* w) {
-  int b[3], v[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) b[k] = grid_index(s[k] * L.block_size_inv);
-  const u32 pool = bc(b[0], b[1], b[2]);
-  if (pool == kInvalid) return false;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float rel = s[k] - static_cast<float>(b[k]) * L.block_size;
-    const int g = grid_index(rel * L.voxel_size_inv);
-    v[k] = g > 15 ? 15 : (g < 0 ? 0 : g);
-  }
-  const u32* vox = L.voxels + (static_cast<size_t>(pool) * kVoxelsPerBlock + static_cast<u32>(v[0] + 16 * (v[1] + 16 * v[2]))) * kWordsPerVoxel;
-  *d = __uint_as_float(vox[0]);
-  *w = __uint_as_float(vox[1]);
-  return *w > 0.0f;
-}
-
 // One branch of the Interpolator (TRI: trilinear, else nearest) at p: distance + weight, and with GRAD the central differences
 // of Interpolator::getGradient at p +- h e_i (h = voxel size), g_i = ((0 + d(p - h e_i) * -1) + d(p + h e_i)) / (2 h), valid
 // when the block of p exists (own_block) and all six samples succeed.  The seven samples run in a loop that is not unrolled:

@@ -1,10 +1,14 @@
-// View scoring for an exploration planner in C++ (header-only, C++14) on top of include/coxgraph_hip_gain.h: the place
-// active_3d_planning gives its ray-casting sensor model and its VoxelWeightEvaluator (coxgraph_sim/config/reconstruction_planner.yaml),
-// here for a whole batch of candidate poses in one call on the GPU.  Rules and arithmetic: DESIGN.md section 7j.
+// What an exploration planner asks of the map, in C++ (header-only, C++14), as coxgraph configures active_3d_planning
+// (coxgraph_sim/config/reconstruction_planner.yaml), each for a whole batch in one call on the GPU:
+//   view scoring -- its ray-casting sensor model and VoxelWeightEvaluator, on include/coxgraph_hip_gain.h;
+//   collision checking -- its VoxbloxMap, the RRTStar generator's segment checks and crop, and the RecheckCollision updater, on
+//   include/coxgraph_hip_collide.h.
 #pragma once
 #include <cmath>
+#include <limits>
 #include <vector>
 
+#include "../../include/coxgraph_hip_collide.h"
 #include "../../include/coxgraph_hip_gain.h"
 #include "coxgraph_hip_adapters.hpp"
 
@@ -104,6 +108,146 @@ class VoxelWeightEvaluator {
   RayCasterSensor sensor_;
   Config config_;
   cox_viewgain_t* h_ = nullptr;
+};
+
+// system_constraints of the yaml (reconstruction_planner.yaml:20-25)
+struct SystemConstraints {
+  float v_max, a_max, yaw_rate_max, yaw_accel_max, collision_radius;
+  SystemConstraints() : v_max(1.0f), a_max(0.5f), yaw_rate_max(0.5f), yaw_accel_max(0.5f), collision_radius(2.0f) {}
+};
+
+// active_3d_planning's VoxbloxMap on an ESDF (or TSDF) layer of this engine: isTraversable / isObserved, one point or a batch
+class VoxbloxMap {
+ public:
+  // the layer must outlive the map; it may be written and may grow between calls
+  explicit VoxbloxMap(cox_layer_t* layer, const SystemConstraints& constraints = SystemConstraints()) : constraints_(constraints) {
+    cox_collide_config c;
+    cox_collide_config_default(&c);
+    c.collision_radius = constraints.collision_radius;
+    check(cox_collide_create(layer, &c, &h_), "VoxbloxMap");
+  }
+  ~VoxbloxMap() { cox_collide_destroy(h_); }
+  VoxbloxMap(const VoxbloxMap&) = delete;
+  VoxbloxMap& operator=(const VoxbloxMap&) = delete;
+
+  const SystemConstraints& constraints() const { return constraints_; }
+  cox_collide_t* handle() const { return h_; }
+
+  // COX_C_* of every position, in one call
+  std::vector<uint8_t> states(const std::vector<Point>& positions) const {
+    std::vector<uint8_t> st(positions.size(), 0);
+    check(cox_collide_points(h_, positions.empty() ? nullptr : positions[0].data(), positions.size(), st.data(), nullptr), "VoxbloxMap::states");
+    return st;
+  }
+  std::vector<bool> isTraversable(const std::vector<Point>& positions) const { return bit(states(positions), COX_C_TRAVERSABLE); }
+  std::vector<bool> isObserved(const std::vector<Point>& positions) const { return bit(states(positions), COX_C_OBSERVED); }
+  // (the orientation argument of the planner's isTraversable is ignored there too)
+  bool isTraversable(const Point& position) const { return isTraversable(std::vector<Point>(1, position))[0]; }
+  bool isObserved(const Point& position) const { return isObserved(std::vector<Point>(1, position))[0]; }
+
+ private:
+  static std::vector<bool> bit(const std::vector<uint8_t>& st, unsigned mask) {
+    std::vector<bool> out(st.size());
+    for (size_t i = 0; i < st.size(); ++i) out[i] = (st[i] & mask) != 0;
+    return out;
+  }
+  SystemConstraints constraints_;
+  cox_collide_t* h_ = nullptr;
+};
+
+// The map side of active_3d_planning's RRTStar trajectory generator and of its RecheckCollision updater
+class RRTStarCollision {
+ public:
+  struct Config {  // the yaml's names and values (trajectory_generator, reconstruction_planner.yaml:27-41)
+    bool collision_optimistic;
+    float clearing_radius;
+    bool crop_segments;
+    float crop_margin, crop_min_length, max_extension_range, sampling_rate;
+    uint32_t max_samples;  // this engine's: sampling intervals a segment may have
+    Config()
+        : collision_optimistic(false), clearing_radius(0.0f), crop_segments(true), crop_margin(0.3f), crop_min_length(0.5f), max_extension_range(1.5f),
+          sampling_rate(20.0f), max_samples(4096) {}
+  };
+  // the stored trajectories of a tree's segments in CSR form and each segment's parent (-1: the root)
+  struct Tree {
+    std::vector<uint64_t> offsets;  // n + 1
+    std::vector<Point> points;
+    std::vector<int32_t> parent;    // n
+    Tree() : offsets(1, 0) {}
+    size_t size() const { return parent.size(); }
+    void addSegment(int32_t parent_index, const std::vector<Point>& trajectory) {
+      points.insert(points.end(), trajectory.begin(), trajectory.end());
+      offsets.push_back(points.size());
+      parent.push_back(parent_index);
+    }
+  };
+
+  RRTStarCollision(cox_layer_t* layer, const SystemConstraints& constraints = SystemConstraints(), const Config& config = Config())
+      : constraints_(constraints), config_(config) {
+    cox_collide_config c;
+    cox_collide_config_default(&c);
+    c.collision_radius = constraints.collision_radius;
+    c.collision_optimistic = config.collision_optimistic ? 1 : 0;
+    c.clearing_radius = config.clearing_radius;
+    c.sample_spacing = constraints.v_max / config.sampling_rate;
+    c.max_samples = config.max_samples;
+    c.max_extension_range = config.max_extension_range;
+    c.crop = config.crop_segments ? 1 : 0;
+    c.crop_margin = config.crop_margin, c.crop_min_length = config.crop_min_length;
+    check(cox_collide_create(layer, &c, &h_), "RRTStarCollision");
+  }
+  ~RRTStarCollision() { cox_collide_destroy(h_); }
+  RRTStarCollision(const RRTStarCollision&) = delete;
+  RRTStarCollision& operator=(const RRTStarCollision&) = delete;
+
+  const Config& config() const { return config_; }
+  cox_collide_t* handle() const { return h_; }
+  // the clearing sphere follows the robot
+  void setRobotPosition(const Point& position) { check(cox_collide_set_clearing_centre(h_, position.data()), "setRobotPosition"); }
+
+  // one record per straight segment starts[i] -> goals[i]
+  std::vector<cox_collide_record> checkSegments(const std::vector<Point>& starts, const std::vector<Point>& goals) const {
+    if (starts.size() != goals.size()) throw std::runtime_error("checkSegments: starts and goals differ in size");
+    std::vector<cox_collide_record> out(starts.size());
+    check(cox_collide_segments(h_, starts.empty() ? nullptr : starts[0].data(), goals.empty() ? nullptr : goals[0].data(), starts.size(), out.data()),
+          "checkSegments");
+    return out;
+  }
+  // connectPoses: the straight segment is traversable at every sample (after the cut to max_extension_range)
+  std::vector<bool> connectPoses(const std::vector<Point>& starts, const std::vector<Point>& goals) const {
+    const std::vector<cox_collide_record> rec = checkSegments(starts, goals);
+    std::vector<bool> out(rec.size());
+    for (size_t i = 0; i < rec.size(); ++i) out[i] = (rec[i].flags & COX_SEG_FEASIBLE) != 0;
+    return out;
+  }
+  // adjustGoalPosition: the goal itself when the segment is free, the cropped goal when enough of it is; success[i] tells
+  std::vector<Point> adjustGoalPositions(const std::vector<Point>& starts, const std::vector<Point>& goals, std::vector<bool>* success) const {
+    const std::vector<cox_collide_record> rec = checkSegments(starts, goals);
+    std::vector<Point> out(rec.size());
+    if (success) success->assign(rec.size(), false);
+    for (size_t i = 0; i < rec.size(); ++i) {
+      for (int k = 0; k < 3; ++k) out[i][k] = rec[i].goal[k];
+      if (success) (*success)[i] = (rec[i].flags & COX_SEG_GOAL) != 0;
+    }
+    return out;
+  }
+  // RecheckCollision: which segments of the tree survive the current map (a collided segment goes with its subtree); keep[i] is
+  // COX_TREE_KEEP, 0 or COX_TREE_INVALID
+  std::vector<uint8_t> recheckCollision(const Tree& tree, std::vector<cox_collide_record>* records = nullptr) const {
+    const size_t n = tree.size();
+    if (tree.offsets.size() != n + 1) throw std::runtime_error("recheckCollision: offsets and parents differ in size");
+    std::vector<uint8_t> keep(n, 0);
+    if (records) records->assign(n, cox_collide_record());
+    check(cox_collide_tree(h_, tree.offsets.data(), tree.parent.data(), n, tree.points.empty() ? nullptr : tree.points[0].data(), tree.points.size(),
+                           records ? records->data() : nullptr, keep.data()),
+          "recheckCollision");
+    return keep;
+  }
+
+ private:
+  SystemConstraints constraints_;
+  Config config_;
+  cox_collide_t* h_ = nullptr;
 };
 
 }  // namespace coxgraph_hip
