@@ -60,8 +60,8 @@ static_assert(cox_plan::kAxisCapSmall == kAxisCapSmall && cox_plan::kTileShift =
 // =================================================================================================
 // A frame is six pipeline stages; up to six frames are in flight, one per stage:
 //   H  bundle hash                            (input only)
-//   P  bundling sort                          (input only)
-//   M  bundle boundaries + sequential means   (-> ray arrays, record offsets)
+//   P  bundling keys + sort + bundle bounds   (input only)
+//   M  sequential means                       (-> ray arrays, record offsets)
 //   T  touch, emit                            (allocates blocks)
 //   R  record partition
 //   U  apply                                  (writes voxels)
@@ -95,7 +95,8 @@ struct FrameSet {  // lives H .. U
   bool used = false;
 };
 struct BundleSet {  // lives H .. M
-  u32 *pslot = nullptr, *skey[2] = {nullptr, nullptr}, *sval[2] = {nullptr, nullptr}, *head = nullptr, *bstart = nullptr;
+  u32 *pslot = nullptr, *skey[2] = {nullptr, nullptr}, *sval[2] = {nullptr, nullptr}, *bstart = nullptr;
+  u32 *hrank = nullptr, *head = nullptr;  // bundle heads (k_bundle_keys): rank inside their tile [pcap], counts per tile [tiles][4]
   SortInfo* sort_info = nullptr;
   hipEvent_t done = nullptr;  // stage M of the frame that used this set
   bool used = false;
@@ -325,8 +326,10 @@ static int alloc_ray_sets(cox_integrator* I, u32 cap) {
     F.fh_first = reinterpret_cast<u32*>(F.fh_keys + I->fh_cap);
     COX_HIP(hipMemset(F.fh_keys, 0xFF, sizeof(u64) * I->fh_cap + sizeof(u32) * I->fh_cap));  // empty; every frame leaves it empty again
   }
-  for (BundleSet& B : I->bs)
-    for (u32** p : {&B.pslot, &B.skey[0], &B.sval[0], &B.skey[1], &B.sval[1], &B.head, &B.bstart}) COX_TRY(dev_realloc(I, p, cap));
+  for (BundleSet& B : I->bs) {
+    for (u32** p : {&B.pslot, &B.skey[0], &B.sval[0], &B.skey[1], &B.sval[1], &B.hrank, &B.bstart}) COX_TRY(dev_realloc(I, p, cap));
+    COX_TRY(dev_realloc(I, &B.head, static_cast<size_t>(4) * (cap / kHeadTile + 1)));
+  }
   for (int k = 0; k < kInputSets; ++k) {
     COX_TRY(dev_realloc(I, &I->own_xyz[k], static_cast<size_t>(cap) * 3));
     COX_TRY(dev_realloc(I, &I->own_rgba[k], static_cast<size_t>(cap) * 4));
@@ -557,12 +560,11 @@ static int stage_hash(const StageCtx& c, hipStream_t s) {
     {
       TimedRegion t(I, COX_KC_BUNDLE_HASH, s);
       // with anti-grazing the hash is read again by touch / emit (stage T), after this frame's pslot may have been reused:
-      // that (rare) configuration keeps the memset; otherwise the frame cleans up after itself (in k_bundle_count, stage M)
+      // that (rare) configuration keeps the memset; otherwise the frame cleans up after itself (BundleBounds, end of stage P)
       const bool self_clean = !I->cfg.enable_anti_grazing;
       if (!self_clean) COX_HIP(hipMemsetAsync(F.fh_keys, 0xFF, sizeof(u64) * I->fh_cap + sizeof(u32) * I->fh_cap, s));
       hipLaunchKernelGGL(k_bundle_insert, grid_for(n), dim3(256), 0, s, F.d_params, I->h_params[c.slot], by_value ? 1 : 0, c.n_dev, F.fh_keys, F.fh_first,
                          I->fh_cap - 1, B.pslot, F.cnt);
-      hipLaunchKernelGGL(k_bundle_keys, grid_for(n), dim3(256), 0, s, F.d_params, F.fh_keys, F.fh_first, B.pslot, B.skey[0], B.sval[0], B.sort_info);
     }
   }
   return COX_OK;
@@ -573,9 +575,22 @@ static int stage_point_sort(const StageCtx& c, hipStream_t s) {
   BundleSet& B = *c.B;
   if (I->method == COX_METHOD_MERGED) {
     const u32 n = I->pcap;
+    const SortWorkspace& ws = (I->st_alt && (c.slot & 1)) ? I->sort_pts_alt : I->sort_pts;
+    // The sort keys are written here, in front of the sort and on its stream, because k_bundle_keys also fills the sort workspace:
+    // the histogram of pass 0, tile by tile as k_rs_hist<11> would -- as long as its tile is the sort's (rs_tile_shift == 0 for
+    // every point count the buffers hold).  It stays in the bundle-hash timing class.
+    const bool counted = static_cast<u64>(n) <= static_cast<u64>(kRsMaxTiles) * kRsTile;
+    {
+      TimedRegion t(I, COX_KC_BUNDLE_HASH, s);
+      hipLaunchKernelGGL(k_bundle_keys, grid_for(n, kHeadTile), dim3(kKeysThreads), 0, s, F.d_params, F.fh_keys, F.fh_first, B.pslot, B.skey[0], B.sval[0], B.hrank, B.head,
+                         B.sort_info, counted ? ws.counts : nullptr, ws.totals);
+    }
+    // the last scatter pass places the bundle heads: it writes the bundle starts and counts, and empties the frame hash
+    const bool self_clean = !I->cfg.enable_anti_grazing;
+    const BundleBounds bounds{F.d_params, B.head, B.hrank, B.pslot, B.bstart, F.cnt, self_clean ? F.fh_keys : nullptr, F.fh_first, I->fh_cap - 1};
     TimedRegion t(I, COX_KC_POINT_SORT, s);
-    (void)radix_sort_pairs<11>(B.skey[0], B.sval[0], B.skey[1], B.sval[1], &F.d_params->n_points, n, n, 0, true, points_sort_passes(I),
-                               (I->st_alt && (c.slot & 1)) ? I->sort_pts_alt : I->sort_pts, B.sort_info, s);
+    (void)radix_sort_pairs<11, BundleBounds>(B.skey[0], B.sval[0], B.skey[1], B.sval[1], &F.d_params->n_points, n, n, 0, true, points_sort_passes(I), ws, B.sort_info,
+                                             s, nullptr, nullptr, counted, bounds);
   }
   return COX_OK;
 }
@@ -586,11 +601,7 @@ static int stage_merge(const StageCtx& c, hipStream_t s) {
   const u32 n = I->pcap;
   if (I->method == COX_METHOD_MERGED) {
     BundleView V{{B.skey[0], B.skey[1]}, {B.sval[0], B.sval[1]}, B.sort_info};
-    // bundle boundaries: heads per tile, then the starts
-    const dim3 gt(std::max<u32>(1, (n + kBoundTile - 1) / kBoundTile));
-    hipLaunchKernelGGL(k_bundle_count, gt, dim3(256), 0, s, F.d_params, V, B.head, B.pslot, F.fh_keys, F.fh_first, I->cfg.enable_anti_grazing ? 0 : 1);
-    hipLaunchKernelGGL(k_bundle_starts, gt, dim3(256), 0, s, F.d_params, V, B.head, B.bstart, F.cnt);
-    {
+    {  // (the bundle boundaries were written by the sort's last pass)
       TimedRegion t(I, COX_KC_MERGE, s);
       hipLaunchKernelGGL(k_bundle_merge, dim3(I->plan.grid_merge), dim3(256), 0, s, F.d_params, V, B.bstart, F.rays, F.cnt,
                          I->plan.walks_pieces() ? (I->plan.small_axis_cap ? kAxisCapSmall : kAxisCapLarge) : 0u);  // (pieces: the rays' piece bounds)

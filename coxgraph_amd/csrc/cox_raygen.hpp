@@ -1,5 +1,5 @@
 // Ray generation (stages H, P, M): one ray per point (simple), or points bundled by terminal voxel and merged by the sequential
-// weighted mean (merged: frame hash, sort keys, bundle boundaries, merge) -- part of cox_integrator.hip (included there, in this
+// weighted mean (merged: frame hash, sort keys + bundle boundaries, merge) -- part of cox_integrator.hip (included there, in this
 // order: the kernels use what is defined above them in that file).
 #pragma once
 
@@ -127,23 +127,101 @@ __global__ void k_params_count(FrameParams* __restrict__ Pp, const u32* __restri
 }
 // sort key of a point = (clearing ? np2 : 0) + first sequence number of its bundle; value = seq.  Also publishes the
 // key width of the bundling sort.
-__global__ void __launch_bounds__(256) k_bundle_keys(const FrameParams* __restrict__ Pp, const u64* __restrict__ fh_keys, const u32* __restrict__ fh_first,
-                                                     const u32* __restrict__ pslot, u32* __restrict__ skey, u32* __restrict__ sval, SortInfo* sort_info) {
+//
+// Everything the frame needs to know about bundle boundaries is known HERE, before the sort.  A point is the HEAD of its bundle
+// when it is the bundle's first visit: fh_first[slot] == seq, i.e. (key & (np2 - 1)) == value -- a property of the pair, which
+// the sort carries along.  The sort is stable and a bundle's points share one key, so the head is also the bundle's first element
+// in sorted order.  The bundle's ordinal is the number of heads with a smaller key = heads of the non-clearing class first, then
+// the clearing ones, each class in sequence order: a prefix count over head flags in SEQUENCE order, which needs nothing from the
+// sorted array.  So one workgroup per tile of kHeadTile consecutive sequence numbers writes
+//   hrank[seq]            for a head: its exclusive rank among the heads of its class inside the tile
+//   tile_heads[tile][4]   heads of the non-clearing class, heads of the clearing class, valid points, (unused)
+// and the scatter kernel of the sort's last pass turns them into bstart[] (BundleBounds below) at the moment it places the head.
+// The tile is also the radix sort's tile (while rs_tile_shift == 0, which the host checks): with `counts` given, the workgroup
+// leaves counts[tile][digit] and the digit totals of the sort's pass 0 exactly as k_rs_hist<11> would, and that launch is skipped.
+constexpr u32 kHeadTile = kRsTile;
+constexpr u32 kHeadTileShift = 11;
+static_assert((1u << kHeadTileShift) == kHeadTile, "kHeadTile");
+constexpr u32 kKeysThreads = 1024;  // 2 rounds of dependent gathers (pslot -> fh_first, fh_keys) per thread: with 256 threads the 8 rounds were 13 us
+constexpr u32 kKeysWaves = kKeysThreads / 64;
+constexpr u32 kHeadRounds = kHeadTile / kKeysThreads;
+__global__ void __launch_bounds__(kKeysThreads) k_bundle_keys(const FrameParams* __restrict__ Pp, const u64* __restrict__ fh_keys, const u32* __restrict__ fh_first,
+                                                     const u32* __restrict__ pslot, u32* __restrict__ skey, u32* __restrict__ sval, u32* __restrict__ hrank,
+                                                     u32* __restrict__ tile_heads, SortInfo* sort_info, u32* __restrict__ counts /* or nullptr */,
+                                                     u32* __restrict__ totals) {
+  __shared__ u32 h[1u << 11];
+  __shared__ u32 wcnt[kHeadRounds][kKeysWaves];  // per (round, wave): heads of either class and valid points, 8 bits each
   const u32 n = Pp->n_points, np2 = Pp->np2;
-  const u32 seq = blockIdx.x * blockDim.x + threadIdx.x;
-  if (seq == 0) {
-    u32 bits = 1;  // clearing bit + log2(np2); kInvalid's low bits exceed every valid key
-    while ((1u << (bits - 1)) < np2) ++bits;
-    sort_info->nbits = bits;
+  u32 nbits = 1;  // clearing bit + log2(np2); kInvalid's low bits exceed every valid key
+  while ((1u << (nbits - 1)) < np2) ++nbits;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    sort_info->nbits = nbits;
     sort_info->parity = 0;
     sort_info->base = 0;
   }
-  if (seq >= n) return;
-  const u32 slot = pslot[mixed_index(seq, n)];  // the bundling sort starts from visiting order: gather on the read side
-  u32 k = kInvalid;
-  if (slot != kInvalid) k = fh_first[slot] + ((fh_keys[slot] >> 63) ? np2 : 0u);
-  skey[seq] = k;
-  sval[seq] = seq;
+  const u32 tile = blockIdx.x;
+  if (tile * kHeadTile >= n) return;
+  int shift;
+  u32 dbits;
+  (void)rs_pass_digits<11>(nbits, 0, &shift, &dbits);  // pass 0: shift 0
+  const u32 kDigits = 1u << dbits;
+  if (counts) {
+    for (u32 d = threadIdx.x; d < kDigits; d += kKeysThreads) h[d] = 0;
+    __syncthreads();
+  }
+  const u32 lane = lane_id(), wave = threadIdx.x >> 6;
+  const u64 lower = (1ull << lane) - 1ull;
+  u32 rank_in_wave[kHeadRounds];
+  u32 head_mask = 0, clr_mask = 0;
+#pragma unroll
+  for (u32 q = 0; q < kHeadRounds; ++q) {  // sequence order inside the tile = (round, wave, lane)
+    const u32 seq = tile * kHeadTile + q * kKeysThreads + threadIdx.x;
+    u32 slot = kInvalid;
+    if (seq < n) slot = pslot[mixed_index(seq, n)];  // the bundling sort starts from visiting order: gather on the read side
+    u32 k = kInvalid;
+    bool head = false, clr = false;
+    if (slot != kInvalid) {
+      const u32 first = fh_first[slot];
+      clr = (fh_keys[slot] >> 63) != 0;
+      k = first + (clr ? np2 : 0u);
+      head = first == seq;
+    }
+    if (seq < n) {
+      skey[seq] = k;
+      sval[seq] = seq;
+      if (counts) atomicAdd(&h[(k >> shift) & (kDigits - 1)], 1u);
+    }
+    const u64 b0 = __ballot(head && !clr), b1 = __ballot(head && clr), bv = __ballot(slot != kInvalid);
+    rank_in_wave[q] = static_cast<u32>(__popcll((clr ? b1 : b0) & lower));
+    head_mask |= (head ? 1u : 0u) << q;
+    clr_mask |= (clr ? 1u : 0u) << q;
+    if (lane == 0) wcnt[q][wave] = static_cast<u32>(__popcll(b0)) | (static_cast<u32>(__popcll(b1)) << 8) | (static_cast<u32>(__popcll(bv)) << 16);
+  }
+  __syncthreads();
+  u32 run0 = 0, run1 = 0, runv = 0;
+#pragma unroll
+  for (u32 q = 0; q < kHeadRounds; ++q) {
+#pragma unroll
+    for (u32 w = 0; w < kKeysWaves; ++w) {
+      if (w == wave && ((head_mask >> q) & 1u)) hrank[tile * kHeadTile + q * kKeysThreads + threadIdx.x] = (((clr_mask >> q) & 1u) ? run1 : run0) + rank_in_wave[q];
+      const u32 c = wcnt[q][w];
+      run0 += c & 255u;
+      run1 += (c >> 8) & 255u;
+      runv += c >> 16;
+    }
+  }
+  if (threadIdx.x == 0) {
+    tile_heads[4 * tile + 0] = run0;
+    tile_heads[4 * tile + 1] = run1;
+    tile_heads[4 * tile + 2] = runv;
+  }
+  if (counts) {
+    for (u32 d = threadIdx.x; d < kDigits; d += kKeysThreads) {
+      const u32 c = h[d];
+      counts[static_cast<size_t>(tile) * kDigits + d] = c;  // the layout of k_rs_hist
+      if (c) atomicAdd(&totals[d], c);
+    }
+  }
 }
 // the two ping-pong buffers of the bundling sort + where its result ended up
 struct BundleView {
@@ -151,84 +229,87 @@ struct BundleView {
   const u32* val[2];
   const SortInfo* info;
 };
-// Bundle boundaries in two launches (round 1 used five: head flags, a three-kernel scan, starts).  A head is a sorted position
-// whose key differs from its predecessor's; a bundle's ordinal is the number of heads before it.
-//   k_bundle_count   per tile of 2048 positions: number of heads
-//   k_bundle_starts  per tile: its base = sum of the counts of the tiles before it (every workgroup adds them up itself --
-//                    a frame has ~150 tiles; a ticketed "last workgroup scans" tail took 12 us, this takes none), heads
-//                    again, in-tile exclusive scan, bstart[base + rank] = position; the last tile publishes the bundle count
-constexpr u32 kBoundTile = 2048;
-__device__ __forceinline__ bool bundle_head(const u32* __restrict__ skey, u32 i, u32 n) {
-  if (i >= n) return false;
-  const u32 k = skey[i];
-  return k != kInvalid && (i == 0 || skey[i - 1] != k);
-}
-// The frame hash is sized for "every point its own bundle" (6 MB) but a frame fills a few thousand slots: instead of a memset
-// per frame, the slots the frame used are put back to empty once its keys have been read (duplicates write the same words) --
-// here, behind the bundling sort (round 2 had a launch of its own for it right behind k_bundle_keys).
-__global__ void __launch_bounds__(256) k_bundle_count(const FrameParams* __restrict__ Pp, BundleView V, u32* __restrict__ tile_sums, const u32* __restrict__ pslot,
-                                                      u64* __restrict__ fh_keys, u32* __restrict__ fh_first, int self_clean) {
-  __shared__ u32 lds[4];
-  const u32 n = Pp->n_points;
-  const u32* __restrict__ skey = V.key[V.info->parity & 1u];
-  const u32 n_tiles = (n + kBoundTile - 1) / kBoundTile;
-  for (u32 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    u32 c = 0;
-#pragma unroll
-    for (u32 q = 0; q < kBoundTile / 256; ++q) {
-      const u32 i = tile * kBoundTile + q * 256 + threadIdx.x;
-      c += bundle_head(skey, i, n) ? 1u : 0u;
-      if (self_clean && i < n) {
-        const u32 slot = pslot[i];
-        if (slot != kInvalid) {
-          fh_keys[slot] = kEmptyKey;
-          fh_first[slot] = 0xFFFFFFFFu;
-        }
+// Hook of the bundling sort's scatter kernel (cox_sort.hpp: RsNoHook), active in the sort's last pass: the position at which a head
+// is placed is the start of its bundle, and its ordinal = (heads of the classes before its own) + (heads of its class in the tiles
+// before its own) + (its rank inside the tile).  Every workgroup adds the tile counts up itself (a frame has ~150 tiles; no ticket,
+// no flag between workgroups); workgroup 0 publishes the totals -- also for an empty frame.  The prefixes of the first kHeadLdsTiles
+// tiles (4 M points) sit in LDS; a head of a later tile adds the remaining counts up from memory.
+// The frame hash is sized for "every point its own bundle" (6 MB) but a frame fills a few thousand slots: instead of a memset per
+// frame, the slots the frame used are put back to empty once its keys have been read -- here, once per bundle, by its head (round 3
+// did it per point behind the sort, round 2 had a launch of its own for it right behind k_bundle_keys).
+constexpr u32 kHeadLdsTiles = 2048;
+struct BundleBounds {
+  static constexpr bool kActive = true;
+  static constexpr u32 kLdsWords = 2 * kHeadLdsTiles + 8;
+  const FrameParams* Pp;
+  const u32* tile_heads;
+  const u32* hrank;
+  const u32* pslot;
+  u32* bstart;
+  Counters* cnt;
+  u64* fh_keys;  // self clean-up of the frame hash; nullptr: the frame does not clean up after itself (anti-grazing)
+  u32* fh_first;
+  u32 fh_mask;
+  __device__ __forceinline__ void begin(u32 n, u32* lds) const {
+    u32* scratch = lds + 2 * kHeadLdsTiles;
+    const u32 n_tiles = (n + kHeadTile - 1) / kHeadTile;
+    u32 carry = 0;
+    for (u32 cls = 0; cls < 2; ++cls) {  // the clearing class goes on where the non-clearing one ends
+      for (u32 b = 0; b < n_tiles; b += 256) {
+        const u32 t = b + threadIdx.x;
+        const u32 v = (t < n_tiles) ? tile_heads[4 * t + cls] : 0u;
+        u32 tot;
+        const u32 ex = block_exclusive_scan<4>(v, &tot, scratch);
+        if (t < n_tiles && t < kHeadLdsTiles) lds[cls * kHeadLdsTiles + t] = carry + ex;
+        carry += tot;
       }
     }
-    u32 tot;
-    (void)block_exclusive_scan<4>(c, &tot, lds);
-    if (threadIdx.x == 0) tile_sums[tile] = tot;
-  }
-}
-__global__ void __launch_bounds__(256) k_bundle_starts(const FrameParams* __restrict__ Pp, BundleView V, const u32* __restrict__ tile_sums, u32* __restrict__ bstart,
-                                                       Counters* cnt) {
-  __shared__ u32 lds[4], lds2[4];
-  const u32 n = Pp->n_points;
-  const u32* __restrict__ skey = V.key[V.info->parity & 1u];
-  const u32 n_tiles = (n + kBoundTile - 1) / kBoundTile;
-  if (n_tiles == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
-    cnt->n_rays = 0;
-    cnt->n_ray_slots = 0;
-  }
-  for (u32 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    u32 below = 0;
-    for (u32 t = threadIdx.x; t < tile; t += 256) below += tile_sums[t];
-    u32 base;
-    (void)block_exclusive_scan<4>(below, &base, lds2);
-    // thread t owns the 8 consecutive positions [tile * 2048 + 8 t, + 8)
-    const u32 i0 = tile * kBoundTile + threadIdx.x * 8;
-    bool h[8];
-    u32 c = 0;
-#pragma unroll
-    for (u32 q = 0; q < 8; ++q) {
-      h[q] = bundle_head(skey, i0 + q, n);
-      c += h[q] ? 1u : 0u;
+    if (blockIdx.x == 0) {
+      u32 v = 0;
+      for (u32 t = threadIdx.x; t < n_tiles; t += 256) v += tile_heads[4 * t + 2];
+      u32 n_valid;
+      (void)block_exclusive_scan<4>(v, &n_valid, scratch);
+      if (threadIdx.x == 0) {
+        cnt->n_rays = carry;  // number of bundles
+        cnt->n_ray_slots = carry;
+        cnt->n_sorted_valid = n_valid;  // invalid keys sort last
+      }
     }
-    u32 tot;
-    u32 rank = base + block_exclusive_scan<4>(c, &tot, lds);
-#pragma unroll
-    for (u32 q = 0; q < 8; ++q) {
-      const u32 i = i0 + q;
-      if (h[q]) bstart[rank++] = i;
-      if (i < n && skey[i] != kInvalid && (i + 1 == n || skey[i + 1] == kInvalid)) cnt->n_sorted_valid = i + 1;  // invalid keys sort last: one writer
+    if (threadIdx.x == 0) {
+      scratch[4] = n;
+      scratch[5] = Pp->np2;
     }
-    if (tile + 1 == n_tiles && threadIdx.x == 0) {
-      cnt->n_rays = base + tot;  // number of bundles
-      cnt->n_ray_slots = base + tot;
+    __syncthreads();
+  }
+  struct Fetched {
+    u32 ord, slot;
+  };
+  __device__ __forceinline__ bool wants(u32 key, u32 val, const u32* lds) const {  // a bundle head
+    const u32 np2 = lds[2 * kHeadLdsTiles + 5];
+    return key != kInvalid && (key & (np2 - 1u)) == val;
+  }
+  __device__ __forceinline__ Fetched fetch(u32 key, u32 val, const u32* lds) const {
+    const u32 n = lds[2 * kHeadLdsTiles + 4], np2 = lds[2 * kHeadLdsTiles + 5];
+    const u32 cls = key >= np2 ? 1u : 0u;
+    const u32 tile = val >> kHeadTileShift;
+    u32 ord;
+    if (tile < kHeadLdsTiles) {
+      ord = lds[cls * kHeadLdsTiles + tile];
+    } else {
+      ord = lds[cls * kHeadLdsTiles + kHeadLdsTiles - 1];
+      for (u32 t = kHeadLdsTiles - 1; t < tile; ++t) ord += tile_heads[4 * t + cls];
+    }
+    ord += hrank[val];
+    return Fetched{ord < n ? ord : kInvalid, fh_keys ? pslot[mixed_index(val, n)] : kInvalid};
+  }
+  __device__ __forceinline__ void commit(const Fetched& f, u32 pos) const {
+    if (f.ord != kInvalid) bstart[f.ord] = pos;
+    if (f.slot <= fh_mask) {  // (kInvalid: an invalid point, or a frame that does not clean up)
+      fh_keys[f.slot] = kEmptyKey;
+      fh_first[f.slot] = 0xFFFFFFFFu;
     }
   }
-}
+};
 
 // two waves per bundle: the sequential weighted mean of its points in visiting order, bit-exact with the
 // single-threaded reference loop

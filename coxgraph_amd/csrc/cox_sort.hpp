@@ -261,15 +261,44 @@ __device__ __forceinline__ u64 match_digit(u32 digit, bool valid, u32 bits) {
   return peers;
 }
 
-template <int RB>
+// Per-element hook of the scatter kernel, for a caller that needs to know where the sort's LAST pass puts an element (the bundling
+// sort: the start of a bundle is the final position of its head, cox_raygen.hpp).  A hook type provides
+//   kActive              compile the hook in (RsNoHook: every other sort compiles to what it was without one)
+//   kLdsWords            LDS the hook wants
+//   begin(n, lds)        called by every workgroup, all threads, before its tiles -- also when it has no tile
+//   wants(key, val, lds) is the hook interested in this pair?  (registers and LDS only)
+//   fetch(key, val, lds) what the hook has to read from memory for a pair it wants (must be harmless for the pair (0, 0))
+//   commit(f, pos)       the pair was written to position pos of the sorted output; f is what fetch returned for it
+// and runs only in the pass that is the last one for the device-side key width (the next pass has no digit left).  The pairs a
+// thread's hook wants are kept until the thread has placed its elements of the tile, and fetched together: a gather per round
+// would put its latency into each of the eight rounds.
+struct RsNoHook {
+  static constexpr bool kActive = false;
+  static constexpr u32 kLdsWords = 1;
+  struct Fetched {};
+  __device__ __forceinline__ void begin(u32, u32*) const {}
+  __device__ __forceinline__ bool wants(u32, u32, const u32*) const { return false; }
+  __device__ __forceinline__ Fetched fetch(u32, u32, const u32*) const { return Fetched{}; }
+  __device__ __forceinline__ void commit(const Fetched&, u32) const {}
+};
+
+template <int RB, class Hook = RsNoHook>
 __global__ void __launch_bounds__(kRsThreads) k_rs_scatter(u32* __restrict__ k0, u32* __restrict__ v0, u32* __restrict__ k1, u32* __restrict__ v1,
                                                            u32* __restrict__ x0, u32* __restrict__ x1 /* optional second value array */,
                                                            const u32* __restrict__ d_n, u32 n_max, int pass, const SortInfo* __restrict__ info, int host_bits,
-                                                           const u32* __restrict__ offsets, u32 tiles_cap, u32* __restrict__ totals) {
+                                                           const u32* __restrict__ offsets, u32 tiles_cap, u32* __restrict__ totals, Hook hook) {
   __shared__ u32 base[kRsWaves][1u << RB];  // first per-wave digit counts, then per-wave running output positions
+  __shared__ u32 hook_lds[Hook::kLdsWords];
   int shift;
   u32 bits;
-  if (!rs_pass_digits<RB>(host_bits >= 0 ? static_cast<u32>(host_bits) : info->nbits, pass, &shift, &bits)) return;
+  const u32 nbits = host_bits >= 0 ? static_cast<u32>(host_bits) : info->nbits;
+  if (!rs_pass_digits<RB>(nbits, pass, &shift, &bits)) return;
+  bool hooked = false;  // workgroup-uniform
+  if constexpr (Hook::kActive) {
+    int next_shift;
+    u32 next_bits;
+    hooked = !rs_pass_digits<RB>(nbits, pass + 1, &next_shift, &next_bits);
+  }
   if (host_bits < 0) shift += static_cast<int>(info->base);
   const u32 kDigits = 1u << bits;
   // the digit totals of this pass were consumed by the offsets kernel: leave them zero for the next sort (no memset per sort)
@@ -290,6 +319,13 @@ __global__ void __launch_bounds__(kRsThreads) k_rs_scatter(u32* __restrict__ k0,
   const u32 n_tiles = (n + tile_elems - 1) / tile_elems;
   const u32 lane = lane_id();
   const u32 wave = threadIdx.x >> 6;
+  if constexpr (Hook::kActive)
+    if (hooked) hook.begin(n, hook_lds);
+  // the pairs of this thread the hook wants: one per round (rounds beyond kRsRounds, i.e. doubled tiles, are committed at once)
+  u32 held_key[kRsRounds], held_val[kRsRounds], held_pos[kRsRounds];
+  u32 held = 0;
+#pragma unroll
+  for (u32 q = 0; q < kRsRounds; ++q) held_key[q] = held_val[q] = held_pos[q] = 0;
   for (u32 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     for (u32 w = 0; w < kRsWaves; ++w)
       for (u32 d = threadIdx.x; d < kDigits; d += kRsThreads) base[w][d] = 0;
@@ -331,10 +367,40 @@ __global__ void __launch_bounds__(kRsThreads) k_rs_scatter(u32* __restrict__ k0,
         keys_out[pos] = key;
         vals_out[pos] = val;
         if (has_x) xtra_out[pos] = xv;
+        if constexpr (Hook::kActive) {
+          if (hooked && hook.wants(key, val, hook_lds)) {
+            if (r < kRsRounds) {
+#pragma unroll
+              for (u32 q = 0; q < kRsRounds; ++q) {  // (no indexing by r: the arrays stay in registers)
+                if (q == r) {
+                  held_key[q] = key;
+                  held_val[q] = val;
+                  held_pos[q] = pos;
+                }
+              }
+              held |= 1u << r;
+            } else {
+              hook.commit(hook.fetch(key, val, hook_lds), pos);
+            }
+          }
+        }
       }
       wave_lds_handover();
       if (valid && lower == 0ull) my_base[digit] += static_cast<u32>(__popcll(peers));  // group leader
       wave_lds_handover();
+    }
+    if constexpr (Hook::kActive) {
+      if (hooked) {
+        typename Hook::Fetched f[kRsRounds];
+#pragma unroll
+        for (u32 q = 0; q < kRsRounds; ++q) f[q] = hook.fetch(held_key[q], held_val[q], hook_lds);  // all gathers in flight together
+#pragma unroll
+        for (u32 q = 0; q < kRsRounds; ++q) {
+          if ((held >> q) & 1u) hook.commit(f[q], held_pos[q]);
+          held_key[q] = held_val[q] = held_pos[q] = 0;
+        }
+        held = 0;
+      }
     }
     __syncthreads();
   }
@@ -355,9 +421,12 @@ static inline size_t sort_totals_words() { return static_cast<size_t>(kRsMaxPass
 // the buffer that holds the result is returned when nbits is known on the host (bits_on_device == false).  Otherwise
 // nbits is read from info->nbits (written by an earlier kernel of the frame), max_passes passes are enqueued (surplus
 // ones exit at once), the result buffer is reported in info->parity (device) and -1 is returned.  RB = 11 or 12.
-template <int RB>
+// pass0_counted: the kernel that wrote the keys has already left counts[tile][digit] and the digit totals of pass 0 in the
+// workspace, exactly as k_rs_hist<RB> would (same tiles, same digit layout): that launch is skipped.  hook: see RsNoHook.
+template <int RB, class Hook = RsNoHook>
 static inline int radix_sort_pairs(u32* k0, u32* v0, u32* k1, u32* v1, const u32* d_n, u32 n_max, u32 n_hint, int host_bits, bool bits_on_device,
-                                   int max_passes, const SortWorkspace& ws, SortInfo* info, hipStream_t s, u32* x0 = nullptr, u32* x1 = nullptr) {
+                                   int max_passes, const SortWorkspace& ws, SortInfo* info, hipStream_t s, u32* x0 = nullptr, u32* x1 = nullptr,
+                                   bool pass0_counted = false, Hook hook = Hook{}) {
   static_assert(RB >= 6 && RB <= static_cast<int>(kRsMaxDigitBits), "digit width");
   const u32 nt = sort_num_tiles(n_hint ? n_hint : 1);
   const u32 grid = nt < 1 ? 1 : (nt > 8192 ? 8192 : nt);
@@ -367,9 +436,11 @@ static inline int radix_sort_pairs(u32* k0, u32* v0, u32* k1, u32* v1, const u32
   const int hb = bits_on_device ? -1 : host_bits;
   for (int p = 0; p < passes; ++p) {
     u32* totals = ws.totals + (static_cast<size_t>(p) << kRsMaxDigitBits);
-    hipLaunchKernelGGL(k_rs_hist<RB>, dim3(grid < 1024 ? grid : 1024), dim3(kRsThreads), 0, s, k0, k1, d_n, n_max, p, info, hb, ws.counts, ws.tiles_cap, totals);
+    if (!(p == 0 && pass0_counted))
+      hipLaunchKernelGGL(k_rs_hist<RB>, dim3(grid < 1024 ? grid : 1024), dim3(kRsThreads), 0, s, k0, k1, d_n, n_max, p, info, hb, ws.counts, ws.tiles_cap, totals);
     hipLaunchKernelGGL(k_rs_offsets<RB>, dim3((1u << RB) / 64u), dim3(kRsOffThreads), 0, s, d_n, n_max, p, info, hb, ws.counts, ws.tiles_cap, totals);
-    hipLaunchKernelGGL(k_rs_scatter<RB>, dim3(grid), dim3(kRsThreads), 0, s, k0, v0, k1, v1, x0, x1, d_n, n_max, p, info, hb, ws.counts, ws.tiles_cap, totals);
+    hipLaunchKernelGGL((k_rs_scatter<RB, Hook>), dim3(grid), dim3(kRsThreads), 0, s, k0, v0, k1, v1, x0, x1, d_n, n_max, p, info, hb, ws.counts, ws.tiles_cap, totals,
+                       hook);
   }
   return bits_on_device ? -1 : (passes & 1);
 }
