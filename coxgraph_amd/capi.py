@@ -321,6 +321,11 @@ class Layer:
         finally:
             cc.close()
 
+    # ---- incremental ESDF (include/coxgraph_hip_esdf.h) ----
+    def esdf_integrator(self, **cfg):
+        """EsdfIntegrator(self.eng, self, **cfg): an ESDF that follows this layer (keywords as esdf())."""
+        return EsdfIntegrator(self.eng, self, **cfg)
+
     def free_points(self, min_distance):
         """createFreePointcloudFromEsdfLayer: (xyz float32[n,3] voxel centres, intensity float32[n] distances), blocks in download
         order, voxels in linear index order."""
@@ -1522,6 +1527,70 @@ class CollisionChecker:
     def tree_dev(self, offsets, parent, n_nodes, xyz, n_points, out, keep, stream=None):
         self.eng.check(self.eng.fn("collide_tree_dev")(self.h, self._ptr(offsets), self._ptr(parent), C.c_uint64(n_nodes), self._ptr(xyz),
                                                        C.c_uint64(n_points), self._ptr(out), self._ptr(keep), self._stream(stream)), "collide_tree_dev")
+
+
+class EsdfUpdateStats(C.Structure):
+    """cox_esdf_update_stats."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_blocks", "n_new_blocks", "n_dirty_blocks", "n_swept_blocks", "n_raise_sweeps", "n_lower_sweeps",
+                                          "n_reset_voxels", "n_changed_voxels")] + [("rebuilt", C.c_uint32), ("pad", C.c_uint32), ("ms", C.c_double)]
+
+    def asdict(self):
+        return {n: (float(self.ms) if n == "ms" else int(getattr(self, n))) for n, _ in self._fields_ if n != "pad"}
+
+
+class _BorrowedLayer(Layer):
+    """A layer owned by another handle: closing it only forgets the pointer (every call on it then fails with INVALID_ARG)."""
+
+    def __init__(self, eng, voxel_size, h):
+        self.eng, self.voxel_size, self.h = eng, voxel_size, h
+
+    def close(self):
+        self.h = C.c_void_p()
+
+
+class EsdfIntegrator:
+    """voxblox EsdfIntegrator::updateFromTsdfLayer (cox_esdf_t): an ESDF bound to a TSDF layer; update() brings it to exactly what
+    layer.esdf(**cfg) would return now.  Keywords as Layer.esdf (default_distance_m follows max_distance_m when only that is given)."""
+
+    def __init__(self, eng, layer, max_distance_m=None, min_distance_m=None, default_distance_m=None, min_weight=None):
+        self.eng, self.tsdf = eng, layer  # (keeps the TSDF alive)
+        cfg = EsdfConfig()
+        eng.fn("esdf_config_default", None)(C.byref(cfg))
+        for k, v in (("max_distance_m", max_distance_m), ("min_distance_m", min_distance_m), ("default_distance_m", default_distance_m), ("min_weight", min_weight)):
+            if v is not None:
+                setattr(cfg, k, v)
+        if max_distance_m is not None and default_distance_m is None:
+            cfg.default_distance_m = max_distance_m
+        self.cfg = cfg
+        self.h = C.c_void_p()
+        self.layer = None
+        eng.check(eng.fn("esdf_create")(layer.h, C.byref(cfg), C.byref(self.h)), "esdf_create")
+        lh = C.c_void_p()
+        eng.check(eng.fn("esdf_layer")(self.h, C.byref(lh)), "esdf_layer")
+        self.layer = _BorrowedLayer(eng, layer.voxel_size, lh)
+
+    def close(self):
+        if self.layer is not None:
+            self.layer.close()  # the borrowed layer dies with the handle: later use is refused
+        if self.h:
+            self.eng.fn("esdf_destroy", None)(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def update(self):
+        if not self.tsdf.h:  # the TSDF was closed under the integrator: refuse, the C handle would read freed memory
+            raise CoxError(-1, "esdf_update (the TSDF layer is closed)")
+        st = EsdfUpdateStats()
+        self.eng.check(self.eng.fn("esdf_update")(self.h, C.byref(st)), "esdf_update")
+        return st.asdict()
+
+    def invalidate(self):
+        self.eng.check(self.eng.fn("esdf_invalidate")(self.h), "esdf_invalidate")
 
 
 # ---- wire-format helpers (voxblox_msgs/Block data words) -----------------------------------------

@@ -27,6 +27,7 @@
 
 #include "../../include/coxgraph_hip.h"
 #include "cox_device.hpp"
+#include "cox_esdf.hpp"
 #include "cox_internal.hpp"
 #include "cox_mc_table.hpp"
 #include "cox_sort.hpp"
@@ -423,25 +424,17 @@ __global__ void __launch_bounds__(256) k_iso_write(const float* __restrict__ ver
 // ---------------------------------------------------------------------------------------------------------------------
 // ESDF
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int kHalo = 18;
+constexpr int kHalo = kEsdfHalo;  // 18: the tile the shared rules of cox_esdf.hpp index
 constexpr int kHaloCells = kHalo * kHalo * kHalo;  // 5832
-constexpr u32 kEsdfFixed = 1u;                     // colour word of a fixed voxel
+constexpr u32 kEsdfFixed = kEsdfFixedFlag;         // colour word of a fixed voxel
 
 __global__ void __launch_bounds__(256) k_esdf_init(u32* __restrict__ voxels, float min_weight, float min_distance, float default_distance) {
   u32* blk = voxels + static_cast<size_t>(blockIdx.x) * kVoxelsPerBlock * kWordsPerVoxel;
   for (u32 v = threadIdx.x; v < kVoxelsPerBlock; v += 256) {
     const float d = __uint_as_float(blk[3 * v]), w = __uint_as_float(blk[3 * v + 1]);
-    float ed = 0.0f, ew = 0.0f;
-    u32 flags = 0;
-    if (!(w < min_weight)) {  // observed
-      ew = 1.0f;
-      if (fabsf(d) < min_distance) {
-        ed = d;
-        flags = kEsdfFixed;
-      } else {
-        ed = (d > 0.0f) ? default_distance : -default_distance;
-      }
-    }
+    float ed, ew;
+    u32 flags;
+    esdf_init_voxel(d, w, min_weight, min_distance, default_distance, &ed, &ew, &flags);  // shared with cox_esdf.hip
     blk[3 * v] = __float_as_uint(ed);
     blk[3 * v + 1] = __float_as_uint(ew);
     blk[3 * v + 2] = flags;
@@ -497,32 +490,9 @@ __global__ void __launch_bounds__(256) k_esdf_sweep(u32* __restrict__ voxels, co
       const int c = x + kHalo * (y + kHalo * z);
       if (st[c] != 1) continue;  // unobserved or fixed
       const float mine = dist[c];
-      float best = mine;
-#pragma unroll
-      for (int dz = -1; dz <= 1; ++dz)
-#pragma unroll
-        for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-          for (int dx = -1; dx <= 1; ++dx) {
-            const int m = (dx != 0) + (dy != 0) + (dz != 0);
-            if (m == 0) continue;
-            const int n = c + dx + kHalo * (dy + kHalo * dz);
-            if (!(st[n] & 1)) continue;
-            const float dn = dist[n];
-            if (!(fabsf(dn) < max_distance)) continue;  // a voxel at or beyond the maximum does not propagate
-            const float step = (m == 1) ? s1 : (m == 2) ? s2 : s3;
-            if (dn > 0.0f) {
-              const float cand = dn + step;
-              if (best > cand) best = cand;
-            } else {
-              const float cand = dn - step;
-              if (best < cand) best = cand;
-            }
-          }
-      // a positive source can only lower a positive voxel, a non-positive source only raise a negative one; the two
-      // candidates never both apply (best moved from `mine` in one direction only if mine had that sign)
-      if (best != mine && ((mine > 0.0f) == (best > 0.0f))) {
-        dist[c] = best;
+      const float now = esdf_relax_voxel(dist, st, c, mine, s1, s2, s3, max_distance);  // shared with cox_esdf.hip
+      if (now != mine) {
+        dist[c] = now;
         any = true;
       }
     }

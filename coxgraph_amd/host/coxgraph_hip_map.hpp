@@ -8,6 +8,7 @@
 #include <memory>
 #include <vector>
 
+#include "../../include/coxgraph_hip_esdf.h"
 #include "../../include/coxgraph_hip_map.h"
 #include "../../include/coxgraph_hip_render.h"
 #include "coxgraph_hip_submap.hpp"
@@ -111,6 +112,40 @@ inline void renderView(cox_layer_t* layer, const Transformation& T_G_C, int widt
                          reinterpret_cast<uint8_t*>(view->color.data()), view->status.data(), &view->stats),
         "renderView");
 }
+
+// voxblox::EsdfIntegrator bound to a TSDF layer (cox_esdf_t): what tsdf_server runs on its update_esdf_every_n_sec timer.  After
+// either update the ESDF layer holds exactly the words cox_esdf_from_tsdf would return for the TSDF as it is.
+class EsdfIntegrator {
+ public:
+  typedef cox_esdf_config Config;
+  EsdfIntegrator(const Config& config, cox_layer_t* tsdf_layer) : h_(nullptr) { check(cox_esdf_create(tsdf_layer, &config, &h_), "EsdfIntegrator"); }
+  EsdfIntegrator(const Config& config, TsdfLayer* tsdf_layer) : h_(nullptr) { check(cox_esdf_create(tsdf_layer->handle(), &config, &h_), "EsdfIntegrator"); }
+  ~EsdfIntegrator() { cox_esdf_destroy(h_); }
+  EsdfIntegrator(const EsdfIntegrator&) = delete;
+  EsdfIntegrator& operator=(const EsdfIntegrator&) = delete;
+
+  // only what the TSDF's changes since the last update can reach is visited
+  cox_esdf_update_stats updateFromTsdfLayer() {
+    cox_esdf_update_stats st;
+    check(cox_esdf_update(h_, &st), "updateFromTsdfLayer");
+    return st;
+  }
+  // from an empty ESDF
+  cox_esdf_update_stats updateFromTsdfLayerBatch() {
+    check(cox_esdf_invalidate(h_), "updateFromTsdfLayerBatch");
+    return updateFromTsdfLayer();
+  }
+  // owned by the integrator; current as of the last update
+  cox_layer_t* getEsdfLayer() const {
+    cox_layer_t* e = nullptr;
+    check(cox_esdf_layer(h_, &e), "getEsdfLayer");
+    return e;
+  }
+  LayerQuery getEsdfMap() const { return LayerQuery(getEsdfLayer()); }
+
+ private:
+  cox_esdf_t* h_;
+};
 
 // coxgraph::client::MapServer without the ROS side: the combined TSDF of a submap collection, its ESDF and the traversable cloud
 class MapServer {
