@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/coxgraph_hip_history.h"
+#include "../../include/coxgraph_hip_selftest.h"
 #include "cox_internal.hpp"
 #include "cox_plan.hpp"
 #include "cox_sort.hpp"
@@ -1696,6 +1697,43 @@ int cox_selftest_division(int device, uint64_t n, uint64_t seed, uint64_t* misma
   (void)hipFree(d);
   *mismatches = h;
   return COX_OK;
+}
+
+// The one-workgroup scans of the ray-generation chain on caller-supplied inputs (tests/test_gpu_sort_scan.py).  It lives here, not in
+// cox_selftest.hip, because k_scan_small and k_scan_small2 are ordinary kernels of cox_frontend.hpp: one translation unit only.
+int cox_selftest_scan_small(int device, const uint32_t* in_a, const uint32_t* in_b, uint32_t len, uint32_t n_max, uint32_t d_n, uint32_t sentinel,
+                            uint32_t* out1_a, uint32_t* out1_b, uint32_t* out2_a, uint32_t* out2_b, uint32_t totals[4]) {
+  COX_ENTRY();
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return COX_ERR_NO_DEVICE;
+  if (!totals || len < std::min(d_n, n_max) || (len && (!in_a || !in_b || !out1_a || !out1_b || !out2_a || !out2_b))) return COX_ERR_INVALID_ARG;
+  COX_HIP(hipSetDevice(device));
+  // one allocation: in_a, in_b, four outputs, the count, four totals
+  const size_t words = std::max<size_t>(len, 1);
+  u32* d = nullptr;
+  COX_HIP(hipMalloc(reinterpret_cast<void**>(&d), (6 * words + 5) * sizeof(u32)));
+  u32 *d_in[2] = {d, d + words}, *d_out = d + 2 * words, *d_cnt = d + 6 * words, *d_tot = d_cnt + 1;
+  const int st = [&]() -> int {
+    if (len) {
+      COX_HIP(hipMemcpy(d_in[0], in_a, len * sizeof(u32), hipMemcpyHostToDevice));
+      COX_HIP(hipMemcpy(d_in[1], in_b, len * sizeof(u32), hipMemcpyHostToDevice));
+    }
+    COX_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d_out), static_cast<int>(sentinel), 4 * words));
+    COX_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d_tot), static_cast<int>(sentinel), 4));
+    COX_HIP(hipMemcpy(d_cnt, &d_n, sizeof(u32), hipMemcpyHostToDevice));
+    COX_HIP(hipDeviceSynchronize());
+    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, nullptr, d_in[0], d_out, d_cnt, n_max, d_tot);
+    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, nullptr, d_in[1], d_out + words, d_cnt, n_max, d_tot + 1);
+    hipLaunchKernelGGL(k_scan_small2, dim3(1), dim3(1024), 0, nullptr, d_in[0], d_out + 2 * words, d_tot + 2, d_in[1], d_out + 3 * words, d_tot + 3, d_cnt, n_max);
+    COX_HIP(hipGetLastError());
+    COX_HIP(hipDeviceSynchronize());
+    uint32_t* outs[4] = {out1_a, out1_b, out2_a, out2_b};
+    for (int k = 0; k < 4 && len; ++k) COX_HIP(hipMemcpy(outs[k], d_out + k * words, len * sizeof(u32), hipMemcpyDeviceToHost));
+    COX_HIP(hipMemcpy(totals, d_tot, 4 * sizeof(u32), hipMemcpyDeviceToHost));
+    return COX_OK;
+  }();
+  (void)hipFree(d);
+  return st;
 }
 
 int cox_integrator_stage_times(cox_integrator_t* I, double ms[2], uint64_t launches[2], int reset) {

@@ -6,6 +6,9 @@
 //
 // The sort is STABLE: equal keys keep their input order.  The engine relies on that to get the
 // canonical per-voxel update order without carrying the order in the key.
+//
+// The contracts stated in this header are held by tests/test_gpu_sort_scan.py, which calls the sort and the scan directly
+// (cox_selftest.hip) and compares them exactly with tests/sort_ref.py.
 #pragma once
 #include "cox_device.hpp"
 
@@ -117,7 +120,7 @@ static inline void exclusive_scan_u32(const u32* in, u32* out, const u32* d_n, u
 }
 
 // ------------------------------------------------------------------------------------------------
-// stable LSD radix sort, RB-bit digits (RB = 8 or 11)
+// stable LSD radix sort, RB-bit digits (instantiated with RB = 11 and RB = 12; a pass may use fewer bits, rs_pass_digits)
 // ------------------------------------------------------------------------------------------------
 constexpr int kRsThreads = 256;
 constexpr int kRsWaves = 4;

@@ -1,0 +1,82 @@
+/* Self-test entry points into the device-wide primitives of libcoxgraph_hip.so: the stable LSD radix sort and the three-launch
+ * exclusive scan (coxgraph_amd/csrc/cox_sort.hpp), and the two one-workgroup scans of the ray-generation chain
+ * (coxgraph_amd/csrc/cox_frontend.hpp).  Only the test suite calls them (tests/test_gpu_sort_scan.py); no product path does.
+ *
+ * Kept apart from coxgraph_hip.h on purpose: these symbols have no counterpart in the CPU checker.  Every entry takes host arrays,
+ * allocates what it needs on `device`, runs the primitive on the null stream exactly as the engine's call sites do, copies back
+ * and frees.  COX_OK or a negative cox_status; no usable GPU -> COX_ERR_NO_DEVICE, checked first; then COX_ERR_INVALID_ARG.
+ * The entries stay inside the primitives' contracts: a call that would break one (base + nbits above 32, a digit width other
+ * than 11 or 12, a missing array) is refused with COX_ERR_INVALID_ARG before anything is launched. */
+#ifndef COXGRAPH_HIP_SELFTEST_H_
+#define COXGRAPH_HIP_SELFTEST_H_
+#include "coxgraph_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* One radix_sort_pairs<rb> call (or `repeat` of them on one workspace).  n = min(d_n, n_max) when use_d_n, else n_max.
+ * Before every sort buffer 0 holds the first n input pairs and `sentinel` in [n, n_max), buffer 1 holds `sentinel` throughout,
+ * hook_pos and hook_aux hold `sentinel` and hook_count holds 0; what is returned is the state after the last sort.  The workspace
+ * is sized as the engine's callers size it (tiles_cap = min(kRsMaxTiles, max(1, ceil(n_max / 2048)))) and its totals are zeroed
+ * once.  Behind the counts matrix the entry keeps a guard of its own, filled with `sentinel`: a sort that needs more rows than
+ * tiles_cap shows up in guard_touched, not in somebody else's memory. */
+typedef struct cox_selftest_sort_args {
+  /* ---- the sort ---- */
+  int32_t rb;              /* digit width the sort is instantiated with: 11 or 12 */
+  uint32_t n_max;          /* capacity of every array below */
+  int32_t use_d_n;         /* 0: d_n == nullptr; 1: the count lives on the device */
+  uint32_t d_n;            /* the device-side count (may exceed n_max: the kernels clamp) */
+  uint32_t n_hint;         /* sizes the grids only */
+  int32_t bits_on_device;  /* 0: host_bits path; 1: SortInfo{nbits, parity = 0, base} on the device, max_passes enqueued */
+  uint32_t nbits;          /* key bits (host_bits on the host path) */
+  uint32_t base;           /* device path only; base + nbits <= 32 */
+  int32_t max_passes;      /* device path only, 1..4 */
+  int32_t pass0_counted;   /* the entry runs k_rs_hist<rb> for pass 0 itself, then sorts with the flag */
+  int32_t hook;            /* 1: sort with the test hook (below) */
+  int32_t repeat;          /* >= 1 sorts on the same workspace, inputs restored before each */
+  const uint32_t* repeat_nbits; /* NULL, or [repeat]: nbits of each repeat (overrides nbits) */
+  uint32_t sentinel;
+  uint32_t pad0;
+  /* ---- inputs, [n_max] ---- */
+  const uint32_t* keys;
+  const uint32_t* vals;
+  const uint32_t* extra;   /* NULL: no second value array (x0 == x1 == nullptr) */
+  const uint32_t* aux;     /* hook only: [max(n_max, 1)], what fetch() reads */
+  /* ---- outputs, [n_max] each; x0/x1 only with extra; hook_* only with hook, [max(n_max, 1)] each ---- */
+  uint32_t* k0;
+  uint32_t* v0;
+  uint32_t* x0;
+  uint32_t* k1;
+  uint32_t* v1;
+  uint32_t* x1;
+  uint32_t* hook_pos;
+  uint32_t* hook_aux;
+  uint32_t* hook_count;    /* commits per value, over all passes of the last sort */
+  int32_t result_buffer;   /* host path: what radix_sort_pairs returned; device path: info->parity afterwards */
+  uint32_t totals_nonzero; /* nonzero words in the whole totals array after the last sort */
+  uint32_t guard_touched;  /* words of the guard behind the counts matrix that no longer hold the sentinel */
+  uint32_t pad1;
+} cox_selftest_sort_args;
+
+/* The test hook: kActive, begin() does nothing, wants(key, val) = (val % 3 == 0), fetch() reads aux[val], commit(f, pos) writes
+ * hook_pos[val] = pos and hook_aux[val] = f and counts the commit in hook_count[val].  Values of wanted pairs must be below
+ * max(n_max, 1). */
+int cox_selftest_sort(int device, cox_selftest_sort_args* args);
+
+/* exclusive_scan_u32 over in[0, n), n as above.  out [n_max]: pre-filled with `sentinel`, or with the input when in_place (then
+ * the scan runs with out == in).  *total: the word d_total points at, pre-filled with `sentinel`; want_total == 0 passes
+ * d_total == nullptr, so the sentinel must come back. */
+int cox_selftest_scan(int device, const uint32_t* in, uint32_t n_max, int use_d_n, uint32_t d_n, uint32_t n_hint, int in_place,
+                      int want_total, uint32_t sentinel, uint32_t* out, uint32_t* total);
+
+/* k_scan_small on in_a, k_scan_small on in_b, and one k_scan_small2 on both, each over min(d_n, n_max) elements of arrays of
+ * `len` words (len >= min(d_n, n_max)).  Outputs are pre-filled with `sentinel`.  totals = {small a, small b, small2 a, small2 b}. */
+int cox_selftest_scan_small(int device, const uint32_t* in_a, const uint32_t* in_b, uint32_t len, uint32_t n_max, uint32_t d_n,
+                            uint32_t sentinel, uint32_t* out1_a, uint32_t* out1_b, uint32_t* out2_a, uint32_t* out2_b,
+                            uint32_t totals[4]);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* COXGRAPH_HIP_SELFTEST_H_ */
