@@ -326,6 +326,11 @@ class Layer:
         """EsdfIntegrator(self.eng, self, **cfg): an ESDF that follows this layer (keywords as esdf())."""
         return EsdfIntegrator(self.eng, self, **cfg)
 
+    # ---- pinhole depth fusion (include/coxgraph_hip_depthfuse.h) ----
+    def depth_integrator(self, **cfg):
+        """DepthIntegrator(self.eng, self, **cfg): fuses depth and colour images of a pinhole camera into this layer."""
+        return DepthIntegrator(self.eng, self, **cfg)
+
     def free_points(self, min_distance):
         """createFreePointcloudFromEsdfLayer: (xyz float32[n,3] voxel centres, intensity float32[n] distances), blocks in download
         order, voxels in linear index order."""
@@ -1591,6 +1596,122 @@ class EsdfIntegrator:
 
     def invalidate(self):
         self.eng.check(self.eng.fn("esdf_invalidate")(self.h), "esdf_invalidate")
+
+
+class DepthFuseConfig(C.Structure):
+    """cox_depthfuse_config."""
+    _fields_ = [("truncation_distance", C.c_float), ("max_weight", C.c_float), ("min_depth_m", C.c_float), ("max_depth_m", C.c_float),
+                ("voxel_carving_enabled", C.c_int32), ("use_const_weight", C.c_int32), ("use_weight_dropoff", C.c_int32),
+                ("interpolation_scheme", C.c_int32), ("adaptive_gap_m", C.c_float), ("reserved", C.c_uint32)]
+
+
+class DepthFuseStats(C.Structure):
+    """cox_depthfuse_stats."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_valid_pixels", "n_candidate_blocks", "n_touched_blocks", "n_new_blocks", "n_updated_voxels",
+                                          "n_coloured_voxels")] + [("kernel_ms", C.c_double)]
+
+    def asdict(self):
+        return {n: (float(self.kernel_ms) if n == "kernel_ms" else int(getattr(self, n))) for n, _ in self._fields_}
+
+
+def depthfuse_config(eng, **cfg):
+    """cox_depthfuse_config_default with fields overridden"""
+    c = DepthFuseConfig()
+    eng.fn("depthfuse_config_default", None)(C.byref(c))
+    for k, v in cfg.items():
+        if not hasattr(c, k):
+            raise AttributeError(k)
+        setattr(c, k, v)
+    return c
+
+
+class DepthIntegrator:
+    """The voxel-projective integrator of a pinhole depth camera (cox_depthfuse_t): cfg are fields of
+    cox_depthfuse_config.  Images are [h, w] float32 z-depths (NaN, 0, negative: nothing there) and [h, w, 4] uint8 r, g, b, a;
+    K = (fx, fy, cx, cy), None: synth.INTRINSICS[(w, h)]."""
+
+    def __init__(self, eng, layer, **cfg):
+        self.eng, self.layer = eng, layer  # (keeps the layer alive)
+        self.cfg = depthfuse_config(eng, **cfg)
+        self.h = C.c_void_p()
+        eng.check(eng.fn("depthfuse_create")(layer.h, C.byref(self.cfg), C.byref(self.h)), "depthfuse_create")
+
+    def close(self):
+        if self.h:
+            self.eng.fn("depthfuse_destroy", None)(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _pose_K(T_G_C, w, h, K):
+        T = np.ascontiguousarray(T_G_C, np.float32)
+        assert T.shape == (7,)
+        if K is None:
+            from . import synth
+            K = synth.INTRINSICS[(w, h)]
+        K = np.ascontiguousarray(K, np.float32)
+        assert K.shape == (4,)
+        return T, K
+
+    def _live(self, what):
+        if not self.layer.h:  # the layer was closed under the integrator: refuse, the C handle would read freed memory
+            raise CoxError(-1, what + " (the layer is closed)")
+
+    def integrate(self, T_G_C, depth, rgba=None, K=None):
+        """cox_depthfuse_integrate: one frame from host images; the update is enqueued, not waited for (sync())."""
+        self._live("depthfuse_integrate")
+        depth = np.ascontiguousarray(depth, np.float32)
+        assert depth.ndim == 2
+        h, w = depth.shape
+        T, K = self._pose_K(T_G_C, w, h, K)
+        if rgba is not None:
+            rgba = np.ascontiguousarray(rgba, np.uint8)
+            assert rgba.shape == (h, w, 4)
+        self.eng.check(self.eng.fn("depthfuse_integrate")(self.h, _fp(T), _fp(depth), None if rgba is None else _fp(rgba), C.c_int(w), C.c_int(h), _fp(K)),
+                       "depthfuse_integrate")
+
+    def integrate_dev(self, T_G_C, depth, rgba, w, h, K=None, stream=None):
+        """cox_depthfuse_integrate_dev: images are torch tensors on the layer's GPU or raw device pointers (ints), rgba may be
+        None; ordered behind `stream` (a torch stream, a raw hipStream_t or None = the null stream), which then waits until the
+        frame has read them."""
+        self._live("depthfuse_integrate_dev")
+
+        def ptr(t):
+            if t is None:
+                return None
+            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        T, K = self._pose_K(T_G_C, w, h, K)
+        s = getattr(stream, "cuda_stream", stream)
+        self.eng.check(self.eng.fn("depthfuse_integrate_dev")(self.h, _fp(T), ptr(depth), ptr(rgba), C.c_int(w), C.c_int(h), _fp(K), C.c_void_p(s or 0)),
+                       "depthfuse_integrate_dev")
+
+    def sync(self):
+        self._live("depthfuse_sync")
+        self.eng.check(self.eng.fn("depthfuse_sync")(self.h), "depthfuse_sync")
+
+    def last_stats(self):
+        self._live("depthfuse_last_stats")
+        st = DepthFuseStats()
+        self.eng.check(self.eng.fn("depthfuse_last_stats")(self.h, C.byref(st)), "depthfuse_last_stats")
+        return st.asdict()
+
+    def pool_order(self):
+        """the layer's block indices int32[n, 3] in pool order"""
+        self._live("depthfuse_pool_order")
+        f = self.eng.fn("depthfuse_pool_order")
+        n = C.c_uint64()
+        st = f(self.h, None, C.c_uint64(0), C.byref(n))
+        if st not in (COX_OK, -7):
+            self.eng.check(st, "depthfuse_pool_order(query)")
+        idx = np.zeros((n.value, 3), np.int32)
+        if n.value:
+            self.eng.check(f(self.h, _fp(idx), C.c_uint64(n.value), C.byref(n)), "depthfuse_pool_order")
+        return idx
 
 
 # ---- wire-format helpers (voxblox_msgs/Block data words) -----------------------------------------

@@ -8,6 +8,7 @@
 #include <memory>
 #include <vector>
 
+#include "../../include/coxgraph_hip_depthfuse.h"
 #include "../../include/coxgraph_hip_esdf.h"
 #include "../../include/coxgraph_hip_map.h"
 #include "../../include/coxgraph_hip_render.h"
@@ -112,6 +113,56 @@ inline void renderView(cox_layer_t* layer, const Transformation& T_G_C, int widt
                          reinterpret_cast<uint8_t*>(view->color.data()), view->status.data(), &view->stats),
         "renderView");
 }
+
+// The other direction: a depth camera's frame into the layer (cox_depthfuse_t) -- every voxel the frustum
+// reaches is projected into the depth image.  Images in renderView's layout; a writer of the layer in call order with the
+// TsdfIntegrators on it.
+class DepthImageIntegrator {
+ public:
+  typedef cox_depthfuse_config Config;
+  static Config defaultConfig() {
+    Config c;
+    cox_depthfuse_config_default(&c);
+    return c;
+  }
+  DepthImageIntegrator(const Config& config, cox_layer_t* layer) : h_(nullptr) { check(cox_depthfuse_create(layer, &config, &h_), "DepthImageIntegrator"); }
+  DepthImageIntegrator(const Config& config, TsdfLayer* layer) : h_(nullptr) { check(cox_depthfuse_create(layer->handle(), &config, &h_), "DepthImageIntegrator"); }
+  ~DepthImageIntegrator() { cox_depthfuse_destroy(h_); }
+  DepthImageIntegrator(const DepthImageIntegrator&) = delete;
+  DepthImageIntegrator& operator=(const DepthImageIntegrator&) = delete;
+
+  // depth: width * height z-depths (NaN, 0, negative: nothing there); colors: as many, or empty to leave the colours alone
+  void integrateDepthImage(const Transformation& T_G_C, const std::vector<float>& depth, const std::vector<Color>& colors, int width, int height,
+                           const float K[4]) {
+    const size_t n = (width > 0 && height > 0) ? static_cast<size_t>(width) * static_cast<size_t>(height) : 0;
+    if (depth.size() != n || (!colors.empty() && colors.size() != n)) check(COX_ERR_INVALID_ARG, "integrateDepthImage");
+    float T[7];
+    T_G_C.pack(T);
+    check(cox_depthfuse_integrate(h_, T, depth.data(), colors.empty() ? nullptr : reinterpret_cast<const uint8_t*>(colors.data()), width, height, K),
+          "integrateDepthImage");
+  }
+  // what renderView produced, fused into this integrator's layer (colours where the view has them)
+  void integrateView(const Transformation& T_G_C, const RenderedView& view, const float K[4], bool with_color = true) {
+    integrateDepthImage(T_G_C, view.depth, with_color ? view.color : std::vector<Color>(), view.width, view.height, K);
+  }
+  // device images on the layer's GPU, ordered behind producer_stream (a hipStream_t; NULL: the null stream)
+  void integrateDepthImageDev(const Transformation& T_G_C, const float* depth_dev, const uint8_t* rgba_dev, int width, int height, const float K[4],
+                              void* producer_stream = nullptr) {
+    float T[7];
+    T_G_C.pack(T);
+    check(cox_depthfuse_integrate_dev(h_, T, depth_dev, rgba_dev, width, height, K, producer_stream), "integrateDepthImageDev");
+  }
+  void sync() { check(cox_depthfuse_sync(h_), "DepthImageIntegrator::sync"); }
+  cox_depthfuse_stats lastStats() {
+    cox_depthfuse_stats st;
+    check(cox_depthfuse_last_stats(h_, &st), "DepthImageIntegrator::lastStats");
+    return st;
+  }
+  cox_depthfuse_t* handle() const { return h_; }
+
+ private:
+  cox_depthfuse_t* h_;
+};
 
 // voxblox::EsdfIntegrator bound to a TSDF layer (cox_esdf_t): what tsdf_server runs on its update_esdf_every_n_sec timer.  After
 // either update the ESDF layer holds exactly the words cox_esdf_from_tsdf would return for the TSDF as it is.

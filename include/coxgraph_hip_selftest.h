@@ -1,8 +1,9 @@
 /* Self-test entry points into the device-wide primitives of libcoxgraph_hip.so: the stable LSD radix sort and the three-launch
  * exclusive scan (coxgraph_amd/csrc/cox_sort.hpp), and the two one-workgroup scans of the ray-generation chain
- * (coxgraph_amd/csrc/cox_frontend.hpp).  Only the test suite calls them (tests/test_gpu_sort_scan.py); no product path does.
+ * (coxgraph_amd/csrc/cox_frontend.hpp); and, last, the depth integrator's candidate box.  Only the test suite calls them
+ * (tests/test_gpu_sort_scan.py, tests/test_depthfuse_abi_cpu.py, tests/test_gpu_depthfuse.py); no product path does.
  *
- * Kept apart from coxgraph_hip.h on purpose: these symbols have no counterpart in the CPU checker.  Every entry takes host arrays,
+ * Kept apart from coxgraph_hip.h on purpose: these symbols have no counterpart in the CPU checker.  Every sort or scan entry takes host arrays,
  * allocates what it needs on `device`, runs the primitive on the null stream exactly as the engine's call sites do, copies back
  * and frees.  COX_OK or a negative cox_status; no usable GPU -> COX_ERR_NO_DEVICE, checked first; then COX_ERR_INVALID_ARG.
  * The entries stay inside the primitives' contracts: a call that would break one (base + nbits above 32, a digit width other
@@ -10,6 +11,7 @@
 #ifndef COXGRAPH_HIP_SELFTEST_H_
 #define COXGRAPH_HIP_SELFTEST_H_
 #include "coxgraph_hip.h"
+#include "coxgraph_hip_depthfuse.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -75,6 +77,14 @@ int cox_selftest_scan(int device, const uint32_t* in, uint32_t n_max, int use_d_
 int cox_selftest_scan_small(int device, const uint32_t* in_a, const uint32_t* in_b, uint32_t len, uint32_t n_max, uint32_t d_n,
                             uint32_t sentinel, uint32_t* out1_a, uint32_t* out1_b, uint32_t* out2_a, uint32_t* out2_b,
                             uint32_t totals[4]);
+
+/* The box of candidate blocks a frame of the depth integrator (coxgraph_hip_depthfuse.h, cox_depthfuse.hip) would visit, computed
+ * on the host: the one entry here that needs no GPU and checks for none.  lo[3] is the box's lowest block index, dims[3] its extent
+ * per axis (x, y, z); candidate i is block (lo.x + i % dims.x, lo.y + (i / dims.x) % dims.y, lo.z + i / (dims.x * dims.y)).  cfg
+ * NULL: the defaults.  Statuses as cox_depthfuse_create and cox_depthfuse_integrate give for the same arguments
+ * (COX_ERR_INVALID_ARG, COX_ERR_INDEX_RANGE). */
+int cox_selftest_depthfuse_box(float voxel_size, const cox_depthfuse_config* cfg, const float T_G_C[7], int w, int height, const float K[4],
+                               int32_t lo[3], uint32_t dims[3]);
 
 #ifdef __cplusplus
 }
