@@ -1212,11 +1212,17 @@ cox_layer* cox_internal_integrator_layer(cox_integrator_t* integ) { return integ
 // streams (in the order that is load-bearing, see below), events and every buffer that does not depend on the point capacity
 static int integrator_init(cox_integrator* I) {
   const IntegratorPlan& P = I->plan;
-  // The input stream (host buffers -> staging sets) is created FIRST, directly in front of the stage streams: the hardware queues of
-  // a process are spread over the four pipes of the compute micro-engine in creation order, so four stage streams created back to
-  // back sit on four different pipes, and the input stream lands on the pipe of the LAST of them -- the apply's (two long kernels
-  // per frame), the partner that minds least (sharing with T/R costs 35 %, with a ray-generation stream 45 %).
-  // `fast` has three stage streams: its input stream has a pipe to itself.
+  // Creation order is load-bearing, and what it buys depends on the queue budget (scripts/queue_probe.hip):
+  //  * Ample queues (16, after cox_runtime_prepare()): every stream has a hardware queue of its own, and the queues of a process are
+  //    spread over the four pipes of the compute micro-engine in creation order.  Four stage streams created back to back sit on four
+  //    different pipes; the input stream (host buffers -> staging sets), created FIRST and directly in front of them, lands on the
+  //    pipe of the LAST of them -- the apply's (two long kernels per frame), the partner that minds least (sharing with T/R costs
+  //    35 %, with a ray-generation stream 45 %).  `fast` has three stage streams: its input stream has a pipe to itself.
+  //  * A tight budget (4 queues, the runtime's default): the null stream keeps one queue and the created streams are dealt onto the
+  //    other three -- the fourth stream of the process onto the queue of the third, the fifth onto the second's.  The plan then has at
+  //    most three streams and NO input stream (an idle stream created first would take one of the three queues for nothing), so the
+  //    streams below have a queue each whenever this integrator's are the first streams the process creates; host inputs are copied
+  //    on the frame's own ray-generation stream.
   if (P.input_stream) COX_HIP(hipStreamCreateWithFlags(&I->st_in, hipStreamNonBlocking));
   if (P.alt_raygen_stream) COX_HIP(hipStreamCreateWithFlags(&I->st_alt, hipStreamNonBlocking));
   for (int k = 0; k < kNumStages; ++k) {
@@ -1321,7 +1327,9 @@ int cox_integrator_create(cox_layer_t* layer, const cox_tsdf_config* cfg, int me
   }
   if (!(cfg->default_truncation_distance > 0.0f) || !(cfg->max_weight > 0.0f) || !(cfg->max_ray_length_m > 0.0f)) return COX_ERR_INVALID_ARG;
   COX_HIP(hipSetDevice(layer->device));
-  cox_integrator* I = new (std::nothrow) cox_integrator(projective ? IntegratorPlan() : cox_plan::resolve_plan(method, *cfg, layer->voxel_size, std::getenv));
+  // (the environment, then the queue budget -- a trailing argument that tests/cpp/plan_smoke.cpp leaves out)
+  const int hw_queues = cox_internal_hw_queues();
+  cox_integrator* I = new (std::nothrow) cox_integrator(projective ? IntegratorPlan() : cox_plan::resolve_plan(method, *cfg, layer->voxel_size, (std::getenv), hw_queues));
   if (!I) return COX_ERR_OUT_OF_MEMORY;
   I->layer = layer;
   I->cfg = *cfg;

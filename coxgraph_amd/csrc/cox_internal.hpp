@@ -147,6 +147,7 @@ bool cox_internal_obs_matches(const cox_obs* O, const cox_layer* L);
 // (PyTorch probes peers / devices during its lazy init and may leave a benign error behind).  Every
 // entry point clears it first so that the check after our own launches only sees our own errors.
 extern "C" bool cox_internal_hip_touched;  // cox_layer.hip: the library has reached the HIP runtime (cox_runtime_prepare comes too late after that)
+int cox_internal_hw_queues();  // cox_layer.hip: hardware queues of this process (GPU_MAX_HW_QUEUES, or the runtime's default of 4)
 static inline void cox_clear_stale_hip_error(const char* where) {
   cox_internal_hip_touched = true;
   const hipError_t e = hipGetLastError();

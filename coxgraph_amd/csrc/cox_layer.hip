@@ -90,6 +90,18 @@ int cox_runtime_prepare(void) {
   return setenv("GPU_MAX_HW_QUEUES", "16", 0) == 0 ? 1 : 0;
 }
 
+}  // extern "C"
+
+// The hardware queues the runtime gives this process: GPU_MAX_HW_QUEUES where it is set (by the host, by cox_runtime_prepare() or
+// by whoever started the process), else the runtime's own default of 4.  The integrators' plans size their stream maps by it.
+int cox_internal_hw_queues() {
+  const char* e = std::getenv("GPU_MAX_HW_QUEUES");
+  const int n = e ? std::atoi(e) : 0;
+  return n >= 1 ? n : 4;
+}
+
+extern "C" {
+
 int cox_device_count(void) {
   COX_ENTRY();
   int n = 0;

@@ -1,5 +1,5 @@
 // Everything the ray-casting integrators (simple, merged, fast) decide when they are created and never change afterwards, resolved
-// ONCE by a pure function of (method, configuration, voxel size, environment).  Host-only C++17, no HIP: tests/cpp/plan_smoke.cpp
+// ONCE by a pure function of (method, configuration, voxel size, environment, hardware queues).  Host-only C++17, no HIP: tests/cpp/plan_smoke.cpp
 // builds it with a plain compiler and checks whole plans, so "which stream map / which layer-update path do I get at 2 cm with
 // COX_STREAMS=3p" has an answer without a GPU.  cox_integrator.hip hands the process environment to resolve_plan and reads nothing else.
 #pragma once
@@ -19,7 +19,7 @@ namespace cox_plan {
 #define COX_PLAN_SWITCHES(X)                                                                                                                   \
   X(APPLY) X(APPLY_WAVE) X(BIG_CHUNK) X(BUCKETS) X(COPY_THREADS) X(DEBUG) X(DEPTH_CONVERT) X(FAST_CAP) X(FAST_FENCE) X(FAST_GROUPS)             \
   X(FAST_ROUNDS) X(FAST_SEQUENTIAL) X(FAST_STREAMS) X(GRAPH) X(GRID_APPLY) X(GRID_APPLY_WAVE) X(GRID_MERGE) X(GRID_TOUCH) X(H2D) X(H2D_GROUPS) \
-  X(INPUT_STREAM) X(NO_GRAPH) X(PARTITION) X(SPLIT_TILES) X(STREAMS) X(STREAM_MAP) X(SUBMIT_THREAD) X(TILE) X(TIMELINE) X(WAVE_TILE_MAX)
+  X(INPUT_STREAM) X(NO_GRAPH) X(PARTITION) X(QUEUES) X(SPLIT_TILES) X(STREAMS) X(STREAM_MAP) X(SUBMIT_THREAD) X(TILE) X(TIMELINE) X(WAVE_TILE_MAX)
 #define COX_PLAN_ENUM(n) k##n,
 #define COX_PLAN_NAME(n) "COX_" #n,
 enum Switch { COX_PLAN_SWITCHES(COX_PLAN_ENUM) kNumSwitches };
@@ -33,6 +33,8 @@ constexpr uint32_t kTileShift = 8, kBigChunk = 4096, kBigChunkMin = 1024;  // co
 constexpr int kFastMaxRounds = 8;
 constexpr uint32_t kFastCap0Max = 32, kFastShortMax = 32, kFastRelaxGroups = 128;  // cox_fast.hpp
 constexpr int kCopyGroups = 8;                                                     // cox_frontend.hpp
+constexpr int kAmpleQueues = 0;      // resolve_plan's queue budget when the caller does not give one: every stream has a queue of its own
+constexpr int kMaxQueueBudget = 64;  // COX_QUEUES above this is malformed
 constexpr int kNumStages = 6;  // H bundle hash | P bundling sort | M bundle boundaries + means | T offsets, touch, emit | R record partition | U apply
 
 // The four implementations of the layer-update half (stages T, R, U) of a frame:
@@ -96,9 +98,11 @@ inline uint32_t max_steps_per_ray(const cox_tsdf_config& cfg, float voxel_size) 
   return static_cast<uint32_t>(std::min(3.0 * per_axis + 1.0, 1.0e6));
 }
 
-// env: anything callable as const char*(const char*) -- the process environment in the engine, a map in the tests
+// env: anything callable as const char*(const char*) -- the process environment in the engine, a map in the tests.
+// hw_queues: the hardware queues the process has (GPU_MAX_HW_QUEUES; the engine asks cox_internal_hw_queues()), kAmpleQueues when
+// every stream may be taken to have a queue of its own.  COX_QUEUES=<n> replaces it.
 template <typename Lookup>
-IntegratorPlan resolve_plan(int method, const cox_tsdf_config& cfg, float voxel_size, Lookup env) {
+IntegratorPlan resolve_plan(int method, const cox_tsdf_config& cfg, float voxel_size, Lookup env, int hw_queues = kAmpleQueues) {
   const char* v[kNumSwitches];
   for (int k = 0; k < kNumSwitches; ++k) v[k] = env(kSwitchNames[k]);
   auto is = [&](Switch s, const char* word) { return v[s] && std::strcmp(v[s], word) == 0; };
@@ -169,8 +173,56 @@ IntegratorPlan resolve_plan(int method, const cox_tsdf_config& cfg, float voxel_
     p.fast.streams = (v[kFAST_STREAMS] && num(kFAST_STREAMS) == 1) ? 1 : 3;
     if (p.fast.streams == 1) map = kOne;
   }
-  std::copy(map, map + kNumStages, p.stage_stream);
   p.input_stream = !(v[kINPUT_STREAM] && num(kINPUT_STREAM) == 0);
+
+  // ---- the queue budget.  The runtime gives the host's null stream a hardware queue to itself and deals every created stream onto
+  // the budget - 1 others (scripts/queue_probe.hip, profiles/r05_queue_probe.txt: at 4 queues the 4th stream of a process lands on
+  // the queue of the 3rd, the 5th on the 2nd's, whether streams came and went before or not), and two stages on one queue run back to
+  // back.  Today's plans create 4 to 5 streams: at 4 queues H P M (even) shared a queue with T R and H P M (odd) with U, while the
+  // input stream, idle on the resident path, had one to itself.  So where the streams do not fit, first the input stream goes (host
+  // inputs are then copied on the frame's own ray-generation stream, COX_INPUT_STREAM=0), then the map steps down to the widest one
+  // that fits.  What the map or the input stream was chosen by (COX_STREAMS, COX_STREAM_MAP, COX_FAST_STREAMS; COX_INPUT_STREAM) stays.
+  // Measured at 4 queues on the commit before the budget existed, through the switches (frames/s, medians of 3-5 runs of bench.py,
+  // profiles/r05_map_sweep.json; "-in" = without input stream):
+  //   merged 5 cm          default 3 218 | default -in 6 421 | H P M x2 | T R U -in 7 300 | H P M | T R U 6 231, -in 6 229 | staged -in 6 432 |
+  //                        H P M | T R | U -in 5 855 | one stream 2 777, -in 4 239
+  //   merged 2 cm 1280x720 default 1 354 | default -in 687 | H P M | T R | U -in 1 769 | H P M | T R U -in 832 | H P M x2 | T R U -in 955 (bimodal: single
+  //                        runs of most maps reach 1 600-1 800, this one did in 3 of 5)
+  //   merged 1 cm          default 705 | default -in 771 | H P M | T R | U -in 793 | H P M | T R U -in 772 | H P M x2 | T R U -in 769
+  //   fast 5 cm            default 2 222 | default -in 2 941 | one stream 1 332, -in 1 740
+  // Budgets other than 4 follow the same rule and are covered by the parity tests, not by measurements of their own.
+  // Stage graphs (COX_GRAPH, opt-in and slower) keep the streams they have always had: a stage is captured on its live stream, and
+  // while one thread captures, the other thread's wait for an event last recorded on that stream is refused by the runtime.  With
+  // T R U (or R U) on one stream that window is most of a frame: COX_STREAMS=2 and COX_STREAM_MAP=000112 with COX_GRAPH=1 return an
+  // error on the commit before this one as well.  Graphs are out of the budget until that is mended.
+  int budget = hw_queues;
+  if (v[kQUEUES]) {
+    char* end = nullptr;
+    const long n = std::strtol(v[kQUEUES], &end, 10);
+    if (end != v[kQUEUES] && *end == '\0' && n >= 1 && n <= kMaxQueueBudget) budget = static_cast<int>(n);
+  }
+  p.use_graphs = v[kGRAPH] != nullptr && v[kNO_GRAPH] == nullptr;
+  if (budget > 0 && !p.use_graphs) {
+    const int room = std::max(1, budget - 1);  // queues beside the null stream's
+    const bool map_chosen = fast ? v[kFAST_STREAMS] != nullptr : chosen;
+    auto streams = [&] { return map[kNumStages - 1] + 1 + (p.alt_raygen_stream ? 1 : 0) + (p.input_stream ? 1 : 0); };
+    if (!v[kINPUT_STREAM] && streams() > room) p.input_stream = false;
+    while (!map_chosen && streams() > room && map != kOne) {
+      if (fast) {  // front | solve | update -> one stream
+        map = kOne;
+        p.fast.streams = 1;
+      } else if (map == kUpdateHeavy) {  // H P M | T | R | U -> H P M | T R | U
+        map = kParity;
+      } else if (map == kParity && p.alt_raygen_stream) {  // H P M x2 | T R | U -> H P M x2 | T R U
+        map = kTwo;
+      } else if (p.alt_raygen_stream) {  // H P M x2 | T R U -> H P M | T R U
+        p.alt_raygen_stream = false;
+      } else {  // H P M | T R | U -> H P M | T R U -> one stream
+        map = map == kParity ? kTwo : kOne;
+      }
+    }
+  }
+  std::copy(map, map + kNumStages, p.stage_stream);
   p.n_streams = p.n_stage_streams() + (p.alt_raygen_stream ? 1 : 0) + (p.input_stream ? 1 : 0);
 
   // ---- fast.  At 5 cm two rounds settle every frame of the benchmark stream; at 2 cm and 1 cm nine frames in ten have a ray that
@@ -196,8 +248,7 @@ IntegratorPlan resolve_plan(int method, const cox_tsdf_config& cfg, float voxel_
     }
   }
 
-  // ---- host side.  Stage graphs measured slightly slower than eager launches (2 936 vs 3 117 frames/s), so opt-in.
-  p.use_graphs = v[kGRAPH] != nullptr && v[kNO_GRAPH] == nullptr;
+  // ---- host side.  Stage graphs measured slightly slower than eager launches (2 936 vs 3 117 frames/s), so opt-in (use_graphs: above).
   p.submit_thread = !(v[kSUBMIT_THREAD] && num(kSUBMIT_THREAD) == 0);
   if (v[kCOPY_THREADS]) p.copy_threads = std::min(15, std::max(0, num(kCOPY_THREADS)));
   p.h2d_kernel = is(kH2D, "kernel");

@@ -386,7 +386,9 @@ int cox_comm_allgather_dev_on(cox_comm_t* comm, const void* send_dev, void* recv
  * calls cox_runtime_prepare() FIRST -- before its first HIP call, before it loads anything that makes one (torch, ...).  It sets
  * GPU_MAX_HW_QUEUES=16 unless the variable is already set, touches nothing else, and returns 1 when the runtime of this process
  * was not yet initialised by this library's knowledge (0: too late to have an effect, or the caller's own value stands).  The
- * library no longer does this behind the host's back when it is loaded (round 2 did: a setenv from a static constructor). */
+ * library no longer does this behind the host's back when it is loaded (round 2 did: a setenv from a static constructor).
+ * Without it an integrator still fits the queues the process has: it reads GPU_MAX_HW_QUEUES (4 when unset) when it is created and
+ * runs on three streams or fewer, without an input stream of its own, where there are fewer than six. */
 int cox_runtime_prepare(void);
 
 /* ---- recover mode: mesh-with-history -> per-pose point clouds -> integrator ------------------ */
