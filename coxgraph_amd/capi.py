@@ -1714,6 +1714,172 @@ class DepthIntegrator:
         return idx
 
 
+# ---- dense stereo (include/coxgraph_hip_stereo.h) -------------------------------------------------
+STEREO_BUFFERS = {"rect_left": 0, "rect_right": 1, "cost_sum": 2, "disparity": 3}  # cox_stereo_buffer
+STEREO_INVALID = 0xFFFF
+
+
+class StereoConfig(C.Structure):
+    """cox_stereo_config."""
+    _fields_ = [("n_disparities", C.c_int32), ("n_paths", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32), ("uniqueness_percent", C.c_int32),
+                ("lr_max_diff", C.c_int32), ("min_depth_m", C.c_float), ("max_depth_m", C.c_float), ("reserved", C.c_uint32)]
+
+
+class StereoStats(C.Structure):
+    """cox_stereo_stats."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_valid_pixels", "n_rejected_uniqueness", "n_rejected_lr", "n_rejected_depth")] + \
+               [(n, C.c_double) for n in ("remap_ms", "census_ms", "paths_ms", "winner_ms", "depth_ms", "frame_ms")]
+
+    def asdict(self):
+        return {n: (float(getattr(self, n)) if t is C.c_double else int(getattr(self, n))) for n, t in self._fields_}
+
+
+class StereoCamera(C.Structure):
+    """cox_stereo_camera."""
+    _fields_ = [("camera_model", C.c_int32), ("distortion_model", C.c_int32), ("intrinsics", C.c_double * 4), ("distortion_coeffs", C.c_double * 4)]
+
+
+class StereoCalibration(C.Structure):
+    """cox_stereo_calibration."""
+    _fields_ = [("cam", StereoCamera * 2), ("T_cn_cnm1", C.c_double * 16)]
+
+
+CAMERA_MODELS = {"pinhole": 0, "omni": 1, "eucm": 2, "ds": 3}
+DISTORTION_MODELS = {"radtan": 0, "equidistant": 1, "fov": 2, "none": 3}
+
+
+def stereo_config(eng, **cfg):
+    """cox_stereo_config_default with fields overridden"""
+    c = StereoConfig()
+    eng.fn("stereo_config_default", None)(C.byref(c))
+    for k, v in cfg.items():
+        if not hasattr(c, k):
+            raise AttributeError(k)
+        setattr(c, k, v)
+    return c
+
+
+def stereo_calibration(chain):
+    """a kalibr camchain as a dict (cam0 / cam1 with camera_model, distortion_model, intrinsics, distortion_coeffs, and cam1's
+    T_cn_cnm1 as 4 x 4) -> cox_stereo_calibration; a StereoCalibration passes through"""
+    if isinstance(chain, StereoCalibration):
+        return chain
+    c = StereoCalibration()
+    for i in (0, 1):
+        cam = chain["cam%d" % i]
+        c.cam[i].camera_model = CAMERA_MODELS.get(cam.get("camera_model", "pinhole"), -1)
+        c.cam[i].distortion_model = DISTORTION_MODELS.get(cam.get("distortion_model", "radtan"), -1)
+        c.cam[i].intrinsics[:] = [float(v) for v in cam["intrinsics"]]
+        c.cam[i].distortion_coeffs[:] = [float(v) for v in cam["distortion_coeffs"]]
+    T = np.asarray(chain["cam1"]["T_cn_cnm1"], np.float64)
+    assert T.shape == (4, 4)
+    c.T_cn_cnm1[:] = T.ravel().tolist()
+    return c
+
+
+def rectify_maps(eng, calibration, w, h, scale=1.0):
+    """cox_stereo_rectify_maps (host only): -> map0, map1 float32 [h, w, 2], K_rect float32[4], the baseline in metres,
+    T_c0_rect float32[7]"""
+    calib = stereo_calibration(calibration)
+    n = max(int(w), 0) * max(int(h), 0)
+    map0, map1 = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
+    K, B, T = np.zeros(4, np.float32), C.c_float(), np.zeros(7, np.float32)
+    eng.check(eng.fn("stereo_rectify_maps")(C.byref(calib), C.c_int(w), C.c_int(h), C.c_double(scale), _fp(map0), _fp(map1), _fp(K), C.byref(B), _fp(T)),
+              "stereo_rectify_maps")
+    return map0.reshape(h, w, 2), map1.reshape(h, w, 2), K, float(B.value), T
+
+
+class StereoMatcher:
+    """Dense stereo of w x h 8-bit pairs (cox_stereo_t); cfg are fields of cox_stereo_config.  Either
+    calibration (a camchain, rectified here with `scale`), or maps = (map0, map1) with K_rect and baseline_m, or neither of them
+    with K_rect and baseline_m: the pairs are rectified already.  After a calibration, K_rect, baseline_m and T_c0_rect are its."""
+
+    def __init__(self, eng, w, h, calibration=None, maps=None, K_rect=None, baseline_m=None, scale=1.0, device=0, **cfg):
+        self.eng, self.w, self.h = eng, int(w), int(h)
+        self.cfg = stereo_config(eng, **cfg)
+        self.T_c0_rect = np.array([1, 0, 0, 0, 0, 0, 0], np.float32)
+        if calibration is not None:
+            assert maps is None
+            m0, m1, K_rect, baseline_m, self.T_c0_rect = rectify_maps(eng, calibration, w, h, scale)
+            maps = (m0, m1)
+        if maps is not None:
+            maps = tuple(np.ascontiguousarray(m, np.float32) for m in maps)
+            assert len(maps) == 2 and all(m.size == 2 * self.w * self.h for m in maps)
+        self.K_rect = np.ascontiguousarray(K_rect, np.float32)
+        assert self.K_rect.shape == (4,)
+        self.baseline_m = float(baseline_m)
+        self.h_ = C.c_void_p()
+        eng.check(eng.fn("stereo_create")(C.c_int(device), C.c_int(w), C.c_int(h), C.byref(self.cfg), None if maps is None else _fp(maps[0]),
+                                          None if maps is None else _fp(maps[1]), _fp(self.K_rect), C.c_float(self.baseline_m), C.byref(self.h_)),
+                  "stereo_create")
+        self._keep = []  # host arrays of the frames in flight
+
+    def close(self):
+        if self.h_:
+            self.eng.fn("stereo_destroy", None)(self.h_)
+            self.h_ = C.c_void_p()
+            self._keep = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def compute_async(self, left, right):
+        """cox_stereo_compute without the wait: -> (depth, rgba, disparity), complete after sync()"""
+        left, right = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
+        assert left.shape == (self.h, self.w) and right.shape == (self.h, self.w)
+        depth = np.empty((self.h, self.w), np.float32)
+        rgba = np.empty((self.h, self.w, 4), np.uint8)
+        disparity = np.empty((self.h, self.w), np.uint16)
+        self.eng.check(self.eng.fn("stereo_compute")(self.h_, _fp(left), _fp(right), _fp(depth), _fp(rgba), _fp(disparity)), "stereo_compute")
+        self._keep.append((left, right, depth, rgba, disparity))
+        return depth, rgba, disparity
+
+    def compute(self, left, right):
+        """one pair of [h, w] uint8 images -> depth float32 [h, w] (NaN: nothing), rgba uint8 [h, w, 4], disparity uint16 [h, w]
+        in 1/16 px (0xFFFF: invalid)"""
+        out = self.compute_async(left, right)
+        self.sync()
+        return out
+
+    def compute_dev(self, left, right, depth, rgba=None, disparity=None, stream=None):
+        """cox_stereo_compute_dev: torch tensors on the matcher's GPU or raw device pointers (ints); ordered behind `stream` (a
+        torch stream, a raw hipStream_t or None = the null stream), which then waits until the frame has read left and right.
+        The outputs are complete after sync()."""
+        def ptr(t):
+            if t is None:
+                return None
+            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        s = getattr(stream, "cuda_stream", stream)
+        self.eng.check(self.eng.fn("stereo_compute_dev")(self.h_, ptr(left), ptr(right), ptr(depth), ptr(rgba), ptr(disparity), C.c_void_p(s or 0)),
+                       "stereo_compute_dev")
+
+    def stream(self):
+        """the matcher's hipStream_t as an int"""
+        return int(self.eng.fn("stereo_stream", C.c_void_p)(self.h_) or 0)
+
+    def sync(self):
+        self.eng.check(self.eng.fn("stereo_sync")(self.h_), "stereo_sync")
+        self._keep = []
+
+    def last_stats(self):
+        st = StereoStats()
+        self.eng.check(self.eng.fn("stereo_last_stats")(self.h_, C.byref(st)), "stereo_last_stats")
+        return st.asdict()
+
+    def download(self, which):
+        """an intermediate of the last frame: "rect_left" / "rect_right" uint8 [h, w], "cost_sum" uint16 [h, w, D], "disparity"
+        uint16 [h, w]"""
+        k = STEREO_BUFFERS[which] if isinstance(which, str) else int(which)
+        shape, dt = {0: ((self.h, self.w), np.uint8), 1: ((self.h, self.w), np.uint8), 2: ((self.h, self.w, int(self.cfg.n_disparities)), np.uint16),
+                     3: ((self.h, self.w), np.uint16)}[k]
+        out = np.empty(shape, dt)
+        self.eng.check(self.eng.fn("stereo_download")(self.h_, C.c_int(k), _fp(out), C.c_uint64(out.nbytes)), "stereo_download")
+        return out
+
+
 # ---- wire-format helpers (voxblox_msgs/Block data words) -----------------------------------------
 def words_to_fields(vox):
     """uint32[...,3] wire words -> (distance f32, weight f32, rgba u8[...,4])."""
