@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "../../include/coxgraph_hip_collide.h"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 #include "cox_interp.hpp"
 
 using namespace cox;
@@ -30,12 +30,6 @@ using namespace cox;
 static_assert(sizeof(cox_collide_record) == 32, "cox_collide_record is 32 bytes");
 
 namespace {
-
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
 
 typedef unsigned long long ull;
 
@@ -52,27 +46,12 @@ struct CollideParams {
   int optimistic, crop;
 };
 
-int device_present() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    return COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
-}
-
-LayerView layer_view(const cox_layer* L) {
-  return LayerView{L->voxels, L->ht_keys, L->ht_vals, L->ht_cap - 1, L->voxel_size, L->voxel_size_inv, L->block_size, L->block_size_inv};
-}
-
 __device__ __forceinline__ float dot_self(float x, float y, float z) { return (x * x + y * y) + z * z; }
 
 // rule S: COX_C_* of the sample p; *dist holds the trilinear distance when COX_C_DISTANCE is set
 __device__ __forceinline__ u32 sample_state(const LayerView& L, const CollideParams& P, const float p[3], float* dist) {
   float sc[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) sc[k] = p[k] * L.block_size_inv;
-  if (!(index_in_range(sc[0]) && index_in_range(sc[1]) && index_in_range(sc[2]))) return COX_C_INVALID;  // NaN, +-inf, beyond the keys
+  if (!block_scaled(L, p, sc)) return COX_C_INVALID;  // NaN, +-inf, beyond the keys
   // the trilinear cell reaches g - 1 .. g + 1, one more voxel on each side for rounding at block faces; the nearest voxel is g
   BlockCache bc{L, {0, 0, 0}, {kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid}, 0u};
   int b[3];
@@ -351,33 +330,11 @@ __global__ void __launch_bounds__(kThreads) k_prune_finish(const u32* __restrict
   if (i < n) keep[i] = prune_keep(words[i]);
 }
 
-bool finite_all(const float* v, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
 bool config_ok(const cox_collide_config& c) {
   const float s[] = {c.collision_radius, c.clearing_radius, c.sample_spacing, c.max_extension_range, c.crop_margin, c.crop_min_length};
   if (!finite_all(s, 6) || !finite_all(c.clearing_centre, 3)) return false;
   if (c.clearing_radius < 0.0f || c.sample_spacing < 0.0f || c.crop_margin < 0.0f || c.crop_min_length < 0.0f) return false;
   return c.max_samples <= kMaxMaxSamples;
-}
-
-template <typename T>
-int dev_grow(T** p, u64* cap, u64 need) {  // contents are not kept
-  if (need <= *cap) return COX_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const hipError_t e = hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    return e == hipErrorOutOfMemory ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-  }
-  *cap = need;
-  return COX_OK;
 }
 
 }  // namespace

@@ -21,7 +21,7 @@
 #include <new>
 
 #include "../../include/coxgraph_hip.h"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 
 namespace {
 struct RcclApi {

@@ -23,18 +23,12 @@
 
 #include "../../include/coxgraph_hip_depthfuse.h"
 #include "../../include/coxgraph_hip_selftest.h"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 #include "cox_sort.hpp"
 
 using namespace cox;
 
 namespace {
-
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
 
 typedef unsigned long long ull;
 
@@ -46,15 +40,6 @@ constexpr size_t kBlockWords = static_cast<size_t>(kVoxelsPerBlock) * kWordsPerV
 constexpr int kCtlTouched = 0, kCtlNew = 1, kCtlValid64 = 2, kCtlUpdated64 = 4, kCtlColoured64 = 6, kCtlWords = 8;
 // behind them, for the host read: the layer's block count and error word as k_df_compact found them
 constexpr int kHostNb = kCtlWords, kHostErr = kCtlWords + 1, kHostWords = kCtlWords + 2;
-
-int device_present() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    return COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
-}
 
 // one frame's constants, by value per launch
 struct DfParams {
@@ -77,11 +62,7 @@ __device__ __forceinline__ bool valid_depth(float d) { return isfinite(d) && d >
 
 // step 2's transform: ((c + w uv) + q.vec x uv) + t'
 __device__ __forceinline__ F3 to_camera(const DfParams& P, F3 c) {
-  const F3 qv{P.iqx, P.iqy, P.iqz};
-  F3 uv = cross3(qv, c);
-  uv = uv + uv;
-  const F3 x = cross3(qv, uv);
-  return F3{((c.x + P.iqw * uv.x) + x.x) + P.itx, ((c.y + P.iqw * uv.y) + x.y) + P.ity, ((c.z + P.iqw * uv.z) + x.z) + P.itz};
+  return quat_transform(P.iqw, P.iqx, P.iqy, P.iqz, F3{P.itx, P.ity, P.itz}, c);
 }
 
 // step 4
@@ -321,12 +302,6 @@ __global__ void __launch_bounds__(kDfThreads) k_df_update(DfParams P, const floa
 }
 
 // ---- host: the candidate box and the cull's planes ---------------------------------------------------------------------
-bool finite_all(const float* v, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
 int check_config(const cox_depthfuse_config& c, float voxel_size) {
   const bool pos_finite = std::isfinite(c.truncation_distance) && c.truncation_distance > 0.0f && std::isfinite(c.max_weight) && c.max_weight > 0.0f &&
                           std::isfinite(c.min_depth_m) && c.min_depth_m > 0.0f && std::isfinite(c.max_depth_m) && c.max_depth_m > 0.0f &&
@@ -407,7 +382,7 @@ struct cox_depthfuse {
   // staging of host images
   float* d_depth = nullptr;
   uint8_t* d_rgba = nullptr;
-  size_t depth_cap = 0, rgba_cap = 0;
+  u64 depth_cap = 0, rgba_cap = 0;  // floats, bytes
   cox_depthfuse_stats last{};
   bool pending = false;   // the last frame's counters are still on the device
   bool timed[2] = {false, false};
@@ -682,18 +657,8 @@ int cox_depthfuse_integrate(cox_depthfuse_t* H, const float T[7], const float* d
   COX_HIP(hipSetDevice(H->device));
   const size_t n_px = static_cast<size_t>(w) * static_cast<size_t>(height);
   COX_HIP(hipStreamSynchronize(H->stream));  // the staging buffers are single: the frame that read them last is done
-  if (n_px > H->depth_cap) {
-    if (H->d_depth) (void)hipFree(H->d_depth);
-    H->d_depth = nullptr, H->depth_cap = 0;
-    COX_HIP(hipMalloc(reinterpret_cast<void**>(&H->d_depth), sizeof(float) * n_px));
-    H->depth_cap = n_px;
-  }
-  if (rgba && n_px > H->rgba_cap) {
-    if (H->d_rgba) (void)hipFree(H->d_rgba);
-    H->d_rgba = nullptr, H->rgba_cap = 0;
-    COX_HIP(hipMalloc(reinterpret_cast<void**>(&H->d_rgba), 4 * n_px));
-    H->rgba_cap = n_px;
-  }
+  COX_TRY(dev_grow(&H->d_depth, &H->depth_cap, n_px));
+  if (rgba) COX_TRY(dev_grow(&H->d_rgba, &H->rgba_cap, 4 * n_px));
   COX_HIP(hipMemcpyAsync(H->d_depth, depth, sizeof(float) * n_px, hipMemcpyHostToDevice, H->stream));
   if (rgba) COX_HIP(hipMemcpyAsync(H->d_rgba, rgba, 4 * n_px, hipMemcpyHostToDevice, H->stream));
   return frame(H, box, T, H->d_depth, rgba ? H->d_rgba : nullptr, w, height, K);

@@ -51,14 +51,27 @@ __device__ __forceinline__ F3 cross3(F3 a, F3 b) { return F3{a.y * b.z - a.z * b
 __device__ __forceinline__ float std_min(float a, float b) { return (b < a) ? b : a; }  // std::min
 __device__ __forceinline__ float std_max(float a, float b) { return (a < b) ? b : a; }  // std::max
 
-// Eigen Quaternion::_transformVector + translation (minkindr transform)
-__device__ __forceinline__ F3 transform_point(const FrameParams& P, F3 v) {
-  const F3 qv{P.qx, P.qy, P.qz};
-  F3 uv = cross3(qv, v);
+// Eigen Quaternion::_transformVector, operation for operation: the one rotation every kernel uses.  The result is
+// (v + qw * uv) + c, and a rigid transform (minkindr) adds its translation to that, one component after the other.
+__device__ __forceinline__ void quat_cross_terms(float qx, float qy, float qz, F3 v, F3& uv, F3& c) {
+  const F3 qv{qx, qy, qz};
+  uv = cross3(qv, v);
   uv = uv + uv;
-  const F3 c = cross3(qv, uv);
-  return F3{((v.x + P.qw * uv.x) + c.x) + P.tx, ((v.y + P.qw * uv.y) + c.y) + P.ty, ((v.z + P.qw * uv.z) + c.z) + P.tz};
+  c = cross3(qv, uv);
 }
+__device__ __forceinline__ F3 quat_rotate(float qw, float qx, float qy, float qz, F3 v) {
+  F3 uv, c;
+  quat_cross_terms(qx, qy, qz, v, uv, c);
+  return F3{(v.x + qw * uv.x) + c.x, (v.y + qw * uv.y) + c.y, (v.z + qw * uv.z) + c.z};
+}
+// Not quat_rotate(...) + t: the sum of component x is formed before component y is begun, which is the order the compiler
+// schedules from.  The results are the same bits either way; the instruction streams are not.
+__device__ __forceinline__ F3 quat_transform(float qw, float qx, float qy, float qz, F3 t, F3 v) {
+  F3 uv, c;
+  quat_cross_terms(qx, qy, qz, v, uv, c);
+  return F3{((v.x + qw * uv.x) + c.x) + t.x, ((v.y + qw * uv.y) + c.y) + t.y, ((v.z + qw * uv.z) + c.z) + t.z};
+}
+__device__ __forceinline__ F3 transform_point(const FrameParams& P, F3 v) { return quat_transform(P.qw, P.qx, P.qy, P.qz, F3{P.tx, P.ty, P.tz}, v); }
 
 // voxblox MixedThreadSafeIndex::getNextIndexImpl
 __device__ __forceinline__ u32 mixed_index(u32 seq, u32 n) {

@@ -26,17 +26,11 @@
 
 #include "../../include/coxgraph_hip_esdf.h"
 #include "cox_esdf.hpp"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 
 using namespace cox;
 
 namespace {
-
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
 
 typedef unsigned long long ull;
 
@@ -46,15 +40,6 @@ constexpr int kCtlMismatch = 0, kCtlDirty = 1, kCtlReset = 2, kCtlChanged = 4, k
               kCtlWords = kCtlSweepActive + kSweepsPerRead;
 constexpr int kHostNb = kCtlWords, kHostErr = kCtlWords + 1, kHostWords = kCtlWords + 2;
 constexpr size_t kBlockWords = static_cast<size_t>(kVoxelsPerBlock) * kWordsPerVoxel;
-
-int device_present() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    return COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
-}
 
 // ---- mirror --------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_esdf_keys_differ(const u64* __restrict__ a, const u64* __restrict__ b, u32 n, u32* __restrict__ flag) {

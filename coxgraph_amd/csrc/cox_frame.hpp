@@ -45,6 +45,7 @@ struct Counters {  // per-frame device counters, zeroed at frame start
 };
 enum : u32 { kShValid = 0, kShUpdates = 1, kShVoxels = 2, kShLong = 3, kShRays = 4, kShMaxBundle = 5, kShMaxRun = 6 };  // 5, 6: maxima, not sums
 
+// the read-write view of the units that write a layer (not the read-only cox::LayerView of cox_interp.hpp, which the gather kernels use)
 struct LayerView {
   u32* voxels;
   u64* ht_keys;

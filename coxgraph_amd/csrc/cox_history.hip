@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "../../include/coxgraph_hip_history.h"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 #include "cox_sort.hpp"
 
 using namespace cox;
@@ -68,41 +68,6 @@ struct cox_obs {
 };
 
 namespace {
-
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
-
-int device_present() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    return COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
-}
-
-template <typename T>
-int dev_alloc(T** p, size_t count) {
-  *p = nullptr;
-  const hipError_t e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    return e == hipErrorOutOfMemory ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
-}
-template <typename T>
-struct DevBuf {  // frees on scope exit
-  T* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t count) { return dev_alloc(&p, count); }
-};
 
 // block and cell of the voxel a scaled coordinate triple falls in
 __device__ __forceinline__ void cell_of(int gx, int gy, int gz, u64* key, u32* cell) {

@@ -32,7 +32,7 @@
 
 #include "../../include/coxgraph_hip_history.h"
 #include "../../include/coxgraph_hip_selftest.h"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 #include "cox_plan.hpp"
 #include "cox_sort.hpp"
 #include "cox_threads.hpp"
@@ -231,12 +231,6 @@ struct cox_integrator {
   uint64_t class_regions[COX_KERNEL_CLASSES] = {};
 };
 
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
-
 // ---- ownership: the only ways the integrator allocates device memory, pinned memory and its fixed events ---------------------
 template <typename T>
 static int dev_realloc(cox_integrator* I, T** p, size_t count) {
@@ -245,12 +239,7 @@ static int dev_realloc(cox_integrator* I, T** p, size_t count) {
   *p = nullptr;
   if (count == 0) return COX_OK;
   if (std::find(I->dev_slots.begin(), I->dev_slots.end(), slot) == I->dev_slots.end()) I->dev_slots.push_back(slot);
-  hipError_t e = hipMalloc(slot, count * sizeof(T));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return (e == hipErrorOutOfMemory) ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
+  return cox_hip_status(hipMalloc(slot, count * sizeof(T)));
 }
 template <typename T>
 static int pinned_realloc(cox_integrator* I, T** p, size_t count) {

@@ -10,12 +10,13 @@
 using cox::u32;
 using cox::u64;
 
+// cox_hip_status is cox_host.hpp's: a unit that uses COX_HIP includes that header
 #define COX_HIP(call)                                  \
   do {                                                 \
     hipError_t e_ = (call);                            \
     if (e_ != hipSuccess) {                            \
       fprintf(stderr, "[coxgraph_hip] %s:%d %s -> %s\n", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
-      return (e_ == hipErrorOutOfMemory) ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE; \
+      return cox_hip_status(e_);                       \
     }                                                  \
   } while (0)
 

@@ -3,10 +3,11 @@
 // expression, so both kernels reproduce the checker bit for bit.
 #pragma once
 #include "cox_device.hpp"
+#include "cox_internal.hpp"
 
 namespace cox {
 
-// the read-only part of a layer a gather kernel needs
+// the read-only part of a layer a gather kernel needs (not the read-write ::LayerView of cox_frame.hpp, which the integrator and the history use)
 struct LayerView {
   const u32* voxels;
   const u64* ht_keys;
@@ -14,6 +15,21 @@ struct LayerView {
   u32 ht_mask;
   float voxel_size, voxel_size_inv, block_size, block_size_inv;
 };
+// read on every call: a layer that grew has new buffers
+inline LayerView layer_view(const cox_layer* L) {
+  return LayerView{L->voxels, L->ht_keys, L->ht_vals, L->ht_cap - 1, L->voxel_size, L->voxel_size_inv, L->block_size, L->block_size_inv};
+}
+
+// pos in blocks; false when a coordinate is NaN, +-inf or beyond the packed keys
+__device__ __forceinline__ bool block_scaled(const LayerView& L, const float pos[3], float sc[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) sc[k] = pos[k] * L.block_size_inv;
+  return index_in_range(sc[0]) && index_in_range(sc[1]) && index_in_range(sc[2]);
+}
+// the same for a caller that has no use for sc (each coordinate is scaled where it is tested)
+__device__ __forceinline__ bool point_in_range(const LayerView& L, const float p[3]) {
+  return index_in_range(p[0] * L.block_size_inv) && index_in_range(p[1] * L.block_size_inv) && index_in_range(p[2] * L.block_size_inv);
+}
 
 static __constant__ float c_interp_table[8][8] = {{1, 0, 0, 0, 0, 0, 0, 0},   {-1, 0, 0, 0, 1, 0, 0, 0},   {-1, 0, 1, 0, 0, 0, 0, 0},
                                                   {-1, 1, 0, 0, 0, 0, 0, 0},  {1, 0, -1, 0, -1, 0, 1, 0},  {1, -1, -1, 1, 0, 0, 0, 0},

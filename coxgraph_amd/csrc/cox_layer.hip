@@ -27,7 +27,7 @@
 
 #include "../../include/coxgraph_hip.h"
 #include "cox_device.hpp"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 
 using namespace cox;
 
@@ -161,8 +161,7 @@ int cox_layer_create(float voxel_size, int voxels_per_side, int device, uint64_t
   int st = COX_OK;
   auto alloc = [&](void** p, size_t bytes) {
     if (st != COX_OK) return;
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) st = (e == hipErrorOutOfMemory) ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
+    st = cox_hip_status(hipMalloc(p, bytes));
   };
   alloc(reinterpret_cast<void**>(&L->voxels), vox_bytes);
   alloc(reinterpret_cast<void**>(&L->ht_keys), sizeof(u64) * L->ht_cap);
@@ -727,11 +726,7 @@ struct RigidParams {
   float qw, qx, qy, qz, tx, ty, tz;
 };
 __device__ __forceinline__ F3 rigid_apply(const RigidParams& T, F3 v) {
-  const F3 qv{T.qx, T.qy, T.qz};
-  F3 uv = cross3(qv, v);
-  uv = uv + uv;
-  const F3 c = cross3(qv, uv);
-  return F3{((v.x + T.qw * uv.x) + c.x) + T.tx, ((v.y + T.qw * uv.y) + c.y) + T.ty, ((v.z + T.qw * uv.z) + c.z) + T.tz};
+  return quat_transform(T.qw, T.qx, T.qy, T.qz, F3{T.tx, T.ty, T.tz}, v);
 }
 __constant__ float c_merge_interp_table[8][8] = {{1, 0, 0, 0, 0, 0, 0, 0},   {-1, 0, 0, 0, 1, 0, 0, 0},   {-1, 0, 1, 0, 0, 0, 0, 0},
                                                  {-1, 1, 0, 0, 0, 0, 0, 0},  {1, 0, -1, 0, -1, 0, 1, 0},  {1, -1, -1, 1, 0, 0, 0, 0},

@@ -19,7 +19,7 @@
 #include <cmath>
 #include <vector>
 
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 #include "cox_sort.hpp"
 
 using namespace cox;
@@ -239,48 +239,22 @@ struct PoseSlice {
 // transformPointcloud(T_Submap_C.inverse(), cloud, out)  (mesh_converter.h:200-203)
 __global__ void __launch_bounds__(256) k_transform(const PoseSlice* __restrict__ poses, const float* __restrict__ cloud_xyz, float* __restrict__ out_xyz) {
   const PoseSlice P = poses[blockIdx.y];
-  const F3 qv{P.qx, P.qy, P.qz};
   for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < P.len; i += gridDim.x * blockDim.x) {
     const size_t s = 3 * (static_cast<size_t>(P.src) + i), d = 3 * (static_cast<size_t>(P.dst) + i);
     const F3 v{cloud_xyz[s], cloud_xyz[s + 1], cloud_xyz[s + 2]};
-    F3 uv = cross3(qv, v);
-    uv = uv + uv;
-    const F3 c = cross3(qv, uv);
-    out_xyz[d] = ((v.x + P.qw * uv.x) + c.x) + P.tx;
-    out_xyz[d + 1] = ((v.y + P.qw * uv.y) + c.y) + P.ty;
-    out_xyz[d + 2] = ((v.z + P.qw * uv.z) + c.z) + P.tz;
+    const F3 r = quat_transform(P.qw, P.qx, P.qy, P.qz, F3{P.tx, P.ty, P.tz}, v);
+    out_xyz[d] = r.x;
+    out_xyz[d + 1] = r.y;
+    out_xyz[d + 2] = r.z;
   }
 }
 
 template <typename T>
-int dev_alloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) count = 1;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return (e == hipErrorOutOfMemory) ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
-}
-template <typename T>
 int dev_upload(T** p, const T* host, size_t count, hipStream_t s) {
-  const int rc = dev_alloc(p, count);
-  if (rc != COX_OK) return rc;
+  COX_TRY(dev_alloc(p, count));
   if (count) COX_HIP(hipMemcpyAsync(*p, host, count * sizeof(T), hipMemcpyHostToDevice, s));
   return COX_OK;
 }
-template <typename T>
-void dev_free(T** p) {
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-}
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
-
 // host helpers: float rotate in the device's operation order (Eigen _transformVector)
 void host_rotate(const float q[4], const float v[3], float out[3]) {
   const float qx = q[1], qy = q[2], qz = q[3];

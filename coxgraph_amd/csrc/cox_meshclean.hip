@@ -22,50 +22,13 @@
 #include <utility>
 
 #include "../../include/coxgraph_hip_mesh.h"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 #include "cox_sort.hpp"
 
 using namespace cox;
 
 namespace {
 
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
-
-template <typename T>
-struct DevBuf {  // frees on scope exit
-  T* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t count) {
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      return e == hipErrorOutOfMemory ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-    }
-    return COX_OK;
-  }
-  T* release() {
-    T* q = p;
-    p = nullptr;
-    return q;
-  }
-};
-
-int device_present() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    return COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
-}
 int finish() {  // every entry point is synchronous
   if (hipStreamSynchronize(nullptr) != hipSuccess || hipGetLastError() != hipSuccess) return COX_ERR_NO_DEVICE;
   return COX_OK;

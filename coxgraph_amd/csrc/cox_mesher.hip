@@ -24,51 +24,13 @@
 #include <vector>
 
 #include "../../include/coxgraph_hip_mesh.h"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 #include "cox_mc_table.hpp"
 #include "cox_sort.hpp"
 
 using namespace cox;
 
 namespace {
-
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
-
-template <typename T>
-struct DevBuf {  // frees on scope exit
-  T* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t count) {
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      return e == hipErrorOutOfMemory ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-    }
-    return COX_OK;
-  }
-  T* release() {
-    T* q = p;
-    p = nullptr;
-    return q;
-  }
-};
-
-int device_present() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    return COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
-}
 
 struct MeshView {
   const u32* voxels;
@@ -338,14 +300,7 @@ __global__ void __launch_bounds__(256) k_mesh_msg(const float* __restrict__ pos,
 struct Xf {
   float qw, qx, qy, qz, tx, ty, tz;
 };
-// Eigen Quaternion::_transformVector (cox_device.hpp transform_point without the translation)
-__device__ __forceinline__ F3 rotate_xf(const Xf& T, F3 v) {
-  const F3 qv{T.qx, T.qy, T.qz};
-  F3 uv = cross3(qv, v);
-  uv = uv + uv;
-  const F3 c = cross3(qv, uv);
-  return F3{(v.x + T.qw * uv.x) + c.x, (v.y + T.qw * uv.y) + c.y, (v.z + T.qw * uv.z) + c.z};
-}
+__device__ __forceinline__ F3 rotate_xf(const Xf& T, F3 v) { return quat_rotate(T.qw, T.qx, T.qy, T.qz, v); }
 // in place when src == dst; otherwise a (moved) copy, colours included
 __global__ void __launch_bounds__(256) k_mesh_transform(const float* __restrict__ pos_in, const float* __restrict__ nrm_in, const uint8_t* __restrict__ rgb_in,
                                                         u64 n, Xf T, int move, float* pos_out, float* nrm_out, uint8_t* rgb_out) {

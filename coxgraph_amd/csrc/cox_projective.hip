@@ -22,7 +22,7 @@
 #include "../../include/coxgraph_hip.h"
 #include "../../include/coxgraph_hip_math.h"
 #include "cox_device.hpp"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 
 using namespace cox;
 
@@ -57,11 +57,7 @@ struct ProjLayer {
 };
 
 __device__ __forceinline__ F3 rigid(float qw, float qx, float qy, float qz, float tx, float ty, float tz, F3 v) {
-  const F3 qv{qx, qy, qz};
-  F3 uv = cross3(qv, v);
-  uv = uv + uv;
-  const F3 c = cross3(qv, uv);
-  return F3{((v.x + qw * uv.x) + c.x) + tx, ((v.y + qw * uv.y) + c.y) + ty, ((v.z + qw * uv.z) + c.z) + tz};
+  return quat_transform(qw, qx, qy, qz, F3{tx, ty, tz}, v);
 }
 __device__ __forceinline__ bool bearing_to_image(const ProjParams& P, float altitude, float azimuth, float* h, float* w) {
   const double H = P.rows, W = P.cols;
@@ -306,11 +302,11 @@ struct cox_projective {
   hipStream_t stream = nullptr;
   u32* range = nullptr;
   u32* touched_slots = nullptr;
-  u32 touched_cap = 0;
+  u64 touched_cap = 0;
   ProjCounters* cnt = nullptr;
   ProjCounters* h_cnt = nullptr;  // pinned
   float* own_xyz = nullptr;
-  u64 xyz_cap = 0;
+  u64 xyz_cap = 0;  // floats
   u32 layer_generation = 0;
   cox_frame_stats last{};
   bool pending = false;
@@ -333,12 +329,6 @@ struct cox_projective {
   cox_obs* obs = nullptr;
   hipEvent_t ev_obs = nullptr;
 };
-
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
 
 void cox_proj_destroy(cox_projective* P) {
   if (!P) return;
@@ -491,10 +481,8 @@ static int proj_enqueue(cox_projective* P, const float T[7], const float* xyz_de
   const bool foreign_writer = cox_layer_order_writer(L, P);
   if (P->layer_generation != L->generation || P->touched_cap < L->ht_cap) {
     COX_HIP(hipStreamSynchronize(s));
-    (void)hipFree(P->touched_slots);
-    P->touched_slots = nullptr;
-    COX_HIP(hipMalloc(reinterpret_cast<void**>(&P->touched_slots), sizeof(u32) * L->ht_cap));
-    P->touched_cap = L->ht_cap;
+    P->touched_cap = 0;  // a new generation gets a new buffer whatever the old one holds
+    COX_TRY(dev_grow(&P->touched_slots, &P->touched_cap, L->ht_cap));
     P->layer_generation = L->generation;
   }
   P->last = cox_frame_stats{};
@@ -609,13 +597,7 @@ int cox_proj_attach_history(cox_projective* P, cox_obs* obs) {
 
 int cox_proj_integrate_host(cox_projective* P, const float T[7], const float* xyz, uint64_t n, int deintegrate) {
   if (P->pending) COX_TRY(proj_finish(P));  // the staging buffer below is single: the frame that used it last is done
-  if (n > P->xyz_cap) {
-    if (P->own_xyz) (void)hipFree(P->own_xyz);
-    P->own_xyz = nullptr;
-    P->xyz_cap = 0;
-    COX_HIP(hipMalloc(reinterpret_cast<void**>(&P->own_xyz), sizeof(float) * 3 * n));
-    P->xyz_cap = n;
-  }
+  COX_TRY(dev_grow(&P->own_xyz, &P->xyz_cap, 3 * n));
   if (n) COX_HIP(hipMemcpyAsync(P->own_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, P->stream));
   COX_TRY(cox_proj_integrate(P, T, P->own_xyz, n, deintegrate));
   return proj_finish(P);

@@ -19,50 +19,13 @@
 #include <vector>
 
 #include "../../include/coxgraph_hip_map.h"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 #include "cox_interp.hpp"
 #include "cox_sort.hpp"
 
 using namespace cox;
 
 namespace {
-
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
-
-template <typename T>
-struct DevBuf {  // frees on scope exit
-  T* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t count) {
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      return e == hipErrorOutOfMemory ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-    }
-    return COX_OK;
-  }
-};
-
-int device_present() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    return COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
-}
-
-LayerView layer_view(const cox_layer* L) {
-  return LayerView{L->voxels, L->ht_keys, L->ht_vals, L->ht_cap - 1, L->voxel_size, L->voxel_size_inv, L->block_size, L->block_size_inv};
-}
 
 // ---- the query kernel ------------------------------------------------------------------------------------------------------
 constexpr int kQueryThreads = 256;
@@ -115,9 +78,7 @@ __global__ void __launch_bounds__(kQueryThreads) k_query(LayerView L, const floa
   if (i >= n) return;
   const float p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
   float sc[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) sc[k] = p[k] * L.block_size_inv;
-  if (!(index_in_range(sc[0]) && index_in_range(sc[1]) && index_in_range(sc[2]))) {  // NaN, +-inf, beyond the packed keys
+  if (!block_scaled(L, p, sc)) {  // NaN, +-inf, beyond the packed keys
     if (status) status[i] = 0;
     return;
   }

@@ -19,7 +19,7 @@
 
 #include "../../include/coxgraph_hip.h"
 #include "cox_device.hpp"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 #include "cox_interp.hpp"
 
 using namespace cox;
@@ -73,9 +73,7 @@ __device__ __forceinline__ PointResult reg_point(const ReadingView& L, const Rel
   const float pos[3] = {(P.R[0] * px + P.R[1] * py) + P.R[2] * pz + P.t[0], (P.R[3] * px + P.R[4] * py) + P.R[5] * pz + P.t[1],
                         (P.R[6] * px + P.R[7] * py) + P.R[8] * pz + P.t[2]};
   float sc[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) sc[k] = pos[k] * L.block_size_inv;
-  if (!(index_in_range(sc[0]) && index_in_range(sc[1]) && index_in_range(sc[2]))) return o;
+  if (!block_scaled(L, pos, sc)) return o;
   int b[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) b[k] = grid_index(sc[k]);
@@ -353,27 +351,6 @@ struct cox_reg {
   u64 batch_cap = 0, bpart_cap = 0;
 };
 
-template <typename T>
-static int dev_grow(T** p, u64* cap, u64 need) {
-  if (need <= *cap) return COX_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T));
-  if (e != hipSuccess) return (e == hipErrorOutOfMemory) ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-  *cap = need;
-  return COX_OK;
-}
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
-
-static ReadingView reading_view(const cox_layer* L) {
-  return ReadingView{L->voxels, L->ht_keys, L->ht_vals, L->ht_cap - 1, L->voxel_size, L->voxel_size_inv, L->block_size, L->block_size_inv};
-}
-
 static int stage_samples(cox_reg* G, const uint32_t* sample_idx, uint64_t n_res, const u32** d_idx_out) {
   *d_idx_out = nullptr;
   if (!sample_idx && G->has_stored) {
@@ -555,7 +532,7 @@ int cox_reg_evaluate(cox_reg_t* G, const double pose_ref[4], const double pose_r
   hipStream_t s = G->stream;
   cox_layer_wait_writes(G->reading, s);  // frames still in flight on the reading layer
   COX_HIP(hipEventRecord(G->ev0, s));
-  hipLaunchKernelGGL(k_reg_evaluate, dim3(nb), dim3(kRegThreads), 0, s, reading_view(G->reading), P, G->ref->pts, d_idx, n, G->no_corr_cost,
+  hipLaunchKernelGGL(k_reg_evaluate, dim3(nb), dim3(kRegThreads), 0, s, layer_view(G->reading), P, G->ref->pts, d_idx, n, G->no_corr_cost,
                      residuals ? G->d_res : nullptr, jac_ref ? G->d_jf : nullptr, jac_read ? G->d_jr : nullptr, G->d_small + 2);
   hipLaunchKernelGGL(k_reg_sum_blocks, dim3(1), dim3(64), 0, s, G->d_small + 2, nb, n, G->d_small);
   if (residuals) hipLaunchKernelGGL(k_reg_scale, dim3((n + 255) / 256), dim3(256), 0, s, G->d_res, static_cast<size_t>(n), G->d_small);
@@ -648,7 +625,7 @@ int cox_reg_normal_eq_begin(cox_reg_t* G, const double pose_ref[4], const double
   hipStream_t s = G->stream;
   cox_layer_wait_writes(G->reading, s);  // frames still in flight on the reading layer
   COX_HIP(hipEventRecord(G->ev0, s));
-  hipLaunchKernelGGL(k_reg_normal_eq, dim3(nb), dim3(kRegThreads), 0, s, reading_view(G->reading), P, G->ref->pts, d_idx, n, G->no_corr_cost,
+  hipLaunchKernelGGL(k_reg_normal_eq, dim3(nb), dim3(kRegThreads), 0, s, layer_view(G->reading), P, G->ref->pts, d_idx, n, G->no_corr_cost,
                      G->d_small + kPartial, G->d_small, G->d_ticket);
   COX_HIP(hipEventRecord(G->ev1, s));
   COX_HIP(hipMemcpyAsync(G->h_small, G->d_small, sizeof(double) * kPartial, hipMemcpyDeviceToHost, s));
@@ -734,7 +711,7 @@ int cox_reg_normal_eq_batch(cox_reg_t* const* regs, uint64_t n, const double* po
     const u32 nb = std::max<u32>(1, std::min<u32>(1024, (nr + kRegThreads - 1) / kRegThreads));  // (the same partition as a call of its own: same bits)
     nb_max = std::max(nb_max, nb);
     RegBatchEntry& E = G0->h_table[c];
-    E.L = reading_view(G->reading);
+    E.L = layer_view(G->reading);
     E.P = make_rel_pose(poses_ref + 4 * c, poses_read + 4 * c);
     E.pts = G->ref->pts;
     E.sample_idx = G->has_stored ? G->d_stored : nullptr;

@@ -16,36 +16,12 @@
 #include <cmath>
 
 #include "../../include/coxgraph_hip_render.h"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 #include "cox_interp.hpp"
 
 using namespace cox;
 
 namespace {
-
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
-
-template <typename T>
-struct DevBuf {  // frees on scope exit
-  T* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t count) {
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      return e == hipErrorOutOfMemory ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-    }
-    return COX_OK;
-  }
-};
 
 struct EventPair {  // destroys on scope exit
   hipEvent_t a = nullptr, b = nullptr;
@@ -54,19 +30,6 @@ struct EventPair {  // destroys on scope exit
     if (b) (void)hipEventDestroy(b);
   }
 };
-
-int device_present() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    return COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
-}
-
-LayerView layer_view(const cox_layer* L) {
-  return LayerView{L->voxels, L->ht_keys, L->ht_vals, L->ht_cap - 1, L->voxel_size, L->voxel_size_inv, L->block_size, L->block_size_inv};
-}
 
 constexpr int kRenderThreads = 256;  // 4 waves: 2 x 2 tiles of 8 x 8 pixels
 constexpr int kTile = 16;
@@ -150,10 +113,6 @@ __device__ __forceinline__ void block_window(const LayerView& L, const float p[3
   }
 }
 
-__device__ __forceinline__ bool point_in_range(const LayerView& L, const float p[3]) {  // false for NaN and +-inf too
-  return index_in_range(p[0] * L.block_size_inv) && index_in_range(p[1] * L.block_size_inv) && index_in_range(p[2] * L.block_size_inv);
-}
-
 // Interpolator::getInterpDistance at s: false when the cell is incomplete or invalid
 __device__ __forceinline__ bool tri_sample(const LayerView& L, const CachedFind& bc, const float s[3], float* d) {
   int b[3];
@@ -181,14 +140,7 @@ __device__ __forceinline__ const u32* containing_voxel(const LayerView& L, const
   return L.voxels + (static_cast<size_t>(pool) * kVoxelsPerBlock + static_cast<u32>(v[0] + 16 * (v[1] + 16 * v[2]))) * kWordsPerVoxel;
 }
 
-// Eigen Quaternion::_transformVector (transform_point of cox_device.hpp without the translation)
-__device__ __forceinline__ F3 rotate(const RenderParams& P, F3 v) {
-  const F3 qv{P.qx, P.qy, P.qz};
-  F3 uv = cross3(qv, v);
-  uv = uv + uv;
-  const F3 c = cross3(qv, uv);
-  return F3{(v.x + P.qw * uv.x) + c.x, (v.y + P.qw * uv.y) + c.y, (v.z + P.qw * uv.z) + c.z};
-}
+__device__ __forceinline__ F3 rotate(const RenderParams& P, F3 v) { return quat_rotate(P.qw, P.qx, P.qy, P.qz, v); }
 
 __global__ void __launch_bounds__(kRenderThreads) k_render(LayerView L, RenderParams P, float* __restrict__ depth, float* __restrict__ normal,
                                                            u32* __restrict__ rgba, uint8_t* __restrict__ status, unsigned long long* __restrict__ stats) {
@@ -343,16 +295,10 @@ __global__ void __launch_bounds__(kRenderThreads) k_render(LayerView L, RenderPa
   }
 }
 
-bool all_finite(const float* a, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(a[i])) return false;
-  return true;
-}
-
 int check_render_args(const cox_layer* L, const float* T, int w, int h, const float* K, const cox_render_config* cfg_in, RenderParams* P) {
   if (!L || !T || !K) return COX_ERR_INVALID_ARG;
   if (w <= 0 || h <= 0 || static_cast<u64>(w) * static_cast<u64>(h) > 0x7FFFFFFFull) return COX_ERR_INVALID_ARG;
-  if (!all_finite(T, 7) || !all_finite(K, 4) || K[0] == 0.0f || K[1] == 0.0f) return COX_ERR_INVALID_ARG;
+  if (!finite_all(T, 7) || !finite_all(K, 4) || K[0] == 0.0f || K[1] == 0.0f) return COX_ERR_INVALID_ARG;
   cox_render_config cfg;
   if (cfg_in)
     cfg = *cfg_in;

@@ -9,36 +9,16 @@
 #include <vector>
 
 #include "../../include/coxgraph_hip_selftest.h"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 #include "cox_sort.hpp"
 
 using namespace cox;
 
 namespace {
 
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
-
 constexpr size_t kGuardWords = size_t{16} << kRsMaxDigitBits;  // sixteen rows of the widest digit behind the counts matrix
 
-struct DevWords {  // frees on scope exit
-  u32* p = nullptr;
-  ~DevWords() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t words) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(words, 1) * sizeof(u32));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      return e == hipErrorOutOfMemory ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-    }
-    return COX_OK;
-  }
-};
+using DevWords = DevBuf<u32>;
 
 int fill(u32* p, u32 value, size_t words) {
   if (words) COX_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p), static_cast<int>(value), words));

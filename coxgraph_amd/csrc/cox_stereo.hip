@@ -23,15 +23,9 @@
 #include <new>
 
 #include "../../include/coxgraph_hip_stereo.h"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 
 namespace {
-
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
 
 typedef unsigned long long ull;
 typedef uint16_t u16;
@@ -51,15 +45,6 @@ constexpr int kStages = 5;        // remap, census, paths, winner, depth
 constexpr int kCntValid = 0, kCntUnique = 1, kCntLr = 2, kCntDepth = 3, kCntWords = 4;
 // k_st_winner's word per pixel: d16 in bits 0-15, d0 in bits 16-24, bit 31: rejected by uniqueness
 constexpr u32 kWinUniqueBit = 1u << 31;
-
-int device_present() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    return COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
-}
 
 // ---- step 1 ------------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kThreads) k_st_remap(const u8* __restrict__ in, const float* __restrict__ map_xy, int w, int h,

@@ -28,7 +28,8 @@
 #include "../../include/coxgraph_hip.h"
 #include "cox_device.hpp"
 #include "cox_esdf.hpp"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
+#include "cox_interp.hpp"
 #include "cox_mc_table.hpp"
 #include "cox_sort.hpp"
 
@@ -36,44 +37,8 @@ using namespace cox;
 
 namespace {
 
-struct TsdfView {
-  const u32* voxels;
-  const u64* ht_keys;
-  const u32* ht_vals;
-  u32 ht_mask;
-  float voxel_size, voxel_size_inv, block_size, block_size_inv;
-};
-TsdfView tsdf_view(const cox_layer* L) {
-  return TsdfView{L->voxels, L->ht_keys, L->ht_vals, L->ht_cap - 1, L->voxel_size, L->voxel_size_inv, L->block_size, L->block_size_inv};
-}
-__device__ __forceinline__ u32 find_pool(const TsdfView& L, int bx, int by, int bz) {
-  const u32 slot = ht_find(L.ht_keys, L.ht_mask, pack_key(bx, by, bz));
-  return slot == kInvalid ? kInvalid : L.ht_vals[slot];
-}
-
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
-
-template <typename T>
-struct DevBuf {  // frees on scope exit
-  T* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t count) {
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      return e == hipErrorOutOfMemory ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-    }
-    return COX_OK;
-  }
-};
+using TsdfView = cox::LayerView;
+__device__ __forceinline__ u32 find_pool(const TsdfView& L, int bx, int by, int bz) { return HtPool{L}(bx, by, bz); }
 
 // block count + pool indices in (z, y, x) order of the block index (the packed key orders that way)
 int sorted_blocks(cox_layer* L, u32* nb_out, std::vector<u64>* keys_sorted, DevBuf<u32>* d_order) {
@@ -302,9 +267,7 @@ __device__ __forceinline__ float iso_interp_member(const float q[8], const float
 }
 __device__ __forceinline__ bool interp_distance_weight(const TsdfView& L, const float pos[3], float* d_out, float* w_out) {
   float sc[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) sc[k] = pos[k] * L.block_size_inv;
-  if (!(index_in_range(sc[0]) && index_in_range(sc[1]) && index_in_range(sc[2]))) return false;
+  if (!block_scaled(L, pos, sc)) return false;
   int b[3], vi[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) b[k] = grid_index(sc[k]);
@@ -581,7 +544,7 @@ int cox_regpoints_from_isosurface(cox_layer_t* L, float min_weight, float vertex
     *out = R;
     return COX_OK;
   }
-  const TsdfView V = tsdf_view(L);
+  const TsdfView V = layer_view(L);
   // 1. vertex count per block -> offsets
   DevBuf<u32> bcount;
   DevBuf<u64> boff;
@@ -680,7 +643,7 @@ int cox_esdf_from_tsdf(const cox_layer_t* tsdf, const cox_esdf_config* cfg_in, c
     if (int st = nbr.alloc(27ull * nb)) return fail(st);
     if (int st = changed.alloc(1)) return fail(st);
     hipLaunchKernelGGL(k_esdf_init, dim3(nb), dim3(256), 0, nullptr, E->voxels, cfg.min_weight, cfg.min_distance_m, cfg.default_distance_m);
-    hipLaunchKernelGGL(k_esdf_neighbors, dim3((27u * nb + 255) / 256), dim3(256), 0, nullptr, tsdf_view(E), E->block_keys, nb, nbr.p);
+    hipLaunchKernelGGL(k_esdf_neighbors, dim3((27u * nb + 255) / 256), dim3(256), 0, nullptr, layer_view(E), E->block_keys, nb, nbr.p);
     const float vs = E->voxel_size;
     const float s1 = 1.0f * vs, s2 = std::sqrt(2.0f) * vs, s3 = std::sqrt(3.0f) * vs;
     // a sweep moves the wavefront at least one block further; the distance field is at most max_distance wide

@@ -22,18 +22,12 @@
 #include <new>
 
 #include "../../include/coxgraph_hip_track.h"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 #include "cox_interp.hpp"
 
 using namespace cox;
 
 namespace {
-
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
 
 constexpr int kTrackThreads = 256;
 constexpr u32 kTrackMaxGroups = COX_TRACK_GRID_PASS / kTrackThreads;  // 256: one per CU
@@ -67,10 +61,6 @@ struct TrackState {
   u32 status, iterations, done, pad;
 };
 
-LayerView layer_view(const cox_layer* L) {
-  return LayerView{L->voxels, L->ht_keys, L->ht_vals, L->ht_cap - 1, L->voxel_size, L->voxel_size_inv, L->block_size, L->block_size_inv};
-}
-
 // scan point i in the sensor frame; false when it is not considered (a coordinate / the depth not finite, depth <= 0)
 __device__ __forceinline__ bool scan_point(const ScanView& S, u32 i, F3* p) {
   if (S.depth) {
@@ -93,9 +83,7 @@ __device__ __forceinline__ bool track_point(const LayerView& L, const FrameParam
   *p_G = pg;
   const float pos[3] = {pg.x, pg.y, pg.z};
   float sc[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) sc[k] = pos[k] * L.block_size_inv;
-  if (!(index_in_range(sc[0]) && index_in_range(sc[1]) && index_in_range(sc[2]))) return false;
+  if (!block_scaled(L, pos, sc)) return false;
   int b[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) b[k] = grid_index(sc[k]);
@@ -356,15 +344,6 @@ __global__ void __launch_bounds__(kTrackThreads) k_track_step(LayerView L, ScanV
   if (threadIdx.x == 0) track_decide<DOF>(tile[0], work, C, st);
 }
 
-int device_present() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    return COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
-}
-
 bool config_ok(const cox_track_config& c) {
   auto nonneg = [](double v) { return v >= 0.0; };  // false for NaN
   return (c.dof == 4 || c.dof == 6) && c.stride >= 1u && nonneg(c.max_abs_distance) && nonneg(c.huber_delta) && nonneg(c.damping) &&
@@ -373,11 +352,9 @@ bool config_ok(const cox_track_config& c) {
 }
 
 bool pose_ok(const float T[7]) {
+  if (!finite_all(T, 7)) return false;
   double nn = 0.0;
-  for (int k = 0; k < 7; ++k) {
-    if (!std::isfinite(T[k])) return false;
-    if (k < 4) nn += static_cast<double>(T[k]) * T[k];
-  }
+  for (int k = 0; k < 4; ++k) nn += static_cast<double>(T[k]) * T[k];
   return nn > 0.0;
 }
 
@@ -395,7 +372,7 @@ struct cox_track {
   double* h_out = nullptr;        // pinned [256]
   u32* d_ticket = nullptr;
   float* d_pts = nullptr;  // staging of cox_track_refine's host points
-  u64 pts_cap = 0;
+  u64 pts_cap = 0;       // floats
 };
 
 namespace {
@@ -601,17 +578,7 @@ int cox_track_refine(cox_track_t* K, const float T_prior[7], const float* xyz, u
   COX_TRY(device_present());
   if (!K || !T_prior || !pose_ok(T_prior) || (n && !xyz) || n > 0x7FFFFFFFull) return COX_ERR_INVALID_ARG;
   COX_HIP(hipSetDevice(K->layer->device));
-  if (n > K->pts_cap) {
-    if (K->d_pts) (void)hipFree(K->d_pts);
-    K->d_pts = nullptr;
-    K->pts_cap = 0;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&K->d_pts), sizeof(float) * 3 * n);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return e == hipErrorOutOfMemory ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-    }
-    K->pts_cap = n;
-  }
+  COX_TRY(dev_grow(&K->d_pts, &K->pts_cap, 3 * n));
   if (n) COX_HIP(hipMemcpyAsync(K->d_pts, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, K->stream));
   ScanView S;
   COX_TRY(points_view(K->d_pts, n, K->cfg.stride, &S));

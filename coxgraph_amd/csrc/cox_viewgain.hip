@@ -26,18 +26,12 @@
 #include <vector>
 
 #include "../../include/coxgraph_hip_gain.h"
-#include "cox_internal.hpp"
+#include "cox_host.hpp"
 #include "cox_interp.hpp"
 
 using namespace cox;
 
 namespace {
-
-#define COX_TRY(expr)              \
-  do {                             \
-    int st_ = (expr);              \
-    if (st_ != COX_OK) return st_; \
-  } while (0)
 
 typedef unsigned long long ull;
 
@@ -73,18 +67,7 @@ struct ViewInfo {  // 64 B
   u32 pad[2];
 };
 
-LayerView layer_view(const cox_layer* L) {
-  return LayerView{L->voxels, L->ht_keys, L->ht_vals, L->ht_cap - 1, L->voxel_size, L->voxel_size_inv, L->block_size, L->block_size_inv};
-}
-
-// Eigen Quaternion::_transformVector (the render's rotate)
-__device__ __forceinline__ F3 rotate(const float q[4], F3 v) {
-  const F3 qv{q[1], q[2], q[3]};
-  F3 uv = cross3(qv, v);
-  uv = uv + uv;
-  const F3 c = cross3(qv, uv);
-  return F3{(v.x + q[0] * uv.x) + c.x, (v.y + q[0] * uv.y) + c.y, (v.z + q[0] * uv.z) + c.z};
-}
+__device__ __forceinline__ F3 rotate(const float q[4], F3 v) { return quat_rotate(q[0], q[1], q[2], q[3], v); }
 
 __device__ __forceinline__ bool coord_in_range(const LayerView& L, float p) { return index_in_range(p * L.block_size_inv); }  // false for NaN, +-inf
 
@@ -278,7 +261,7 @@ __global__ void __launch_bounds__(kThreads) k_vg_march(LayerView L, GainParams P
       float p[3];
 #pragma unroll
       for (int c = 0; c < 3; ++c) p[c] = o[c] + d * dir[c];
-      if (!(coord_in_range(L, p[0]) && coord_in_range(L, p[1]) && coord_in_range(L, p[2]))) break;  // left the index range (or NaN)
+      if (!point_in_range(L, p)) break;  // left the index range (or NaN)
       ++n_smp;
       int b[3], vv[3];
 #pragma unroll
@@ -433,53 +416,22 @@ __global__ void __launch_bounds__(kCompactThreads) k_vg_compact(LayerView L, Gai
   if (tid == 0) *n_out = base;
 }
 
-bool all_finite(const float* a, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(a[i])) return false;
-  return true;
-}
-
-int device_present() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    return COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
-}
-
 bool config_ok(const cox_viewgain_config& c, float voxel_size) {
   if (c.w <= 0 || c.h <= 0 || static_cast<u64>(c.w) * static_cast<u64>(c.h) > 0x7FFFFFFFull) return false;
-  if (!all_finite(c.K, 4) || c.K[0] == 0.0f || c.K[1] == 0.0f) return false;
+  if (!finite_all(c.K, 4) || c.K[0] == 0.0f || c.K[1] == 0.0f) return false;
   const float scalars[] = {c.min_range,         c.ray_length,  c.ray_step,    c.min_weight, c.surface_distance, c.frontier_voxel_weight, c.new_voxel_weight,
                            c.min_impact_factor, c.ray_angle_x, c.ray_angle_y};
-  if (!all_finite(scalars, 10)) return false;
+  if (!finite_all(scalars, 10)) return false;
   if (!(c.ray_length > c.min_range) || c.min_range < 0.0f || c.ray_step < 0.0f) return false;
   if (!(c.ray_angle_x * c.ray_angle_y > 0.0f)) return false;
   const float step = c.ray_step == 0.0f ? voxel_size : c.ray_step;
   if (!(c.ray_length / step <= kMaxSteps)) return false;  // float(k) stays exact and the march ends
   if (c.use_box) {
-    if (!all_finite(c.box_min, 3) || !all_finite(c.box_max, 3)) return false;
+    if (!finite_all(c.box_min, 3) || !finite_all(c.box_max, 3)) return false;
     for (int k = 0; k < 3; ++k)
       if (c.box_min[k] > c.box_max[k]) return false;
   }
   return true;
-}
-
-template <typename T>
-int dev_grow(T** p, u64* cap, u64 need) {  // contents are not kept
-  if (need <= *cap) return COX_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const hipError_t e = hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    return e == hipErrorOutOfMemory ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-  }
-  *cap = need;
-  return COX_OK;
 }
 
 }  // namespace
@@ -645,7 +597,7 @@ int cox_viewgain_evaluate(cox_viewgain_t* H, const float* T_G_C, uint64_t n_view
   if (n_views == 0) return COX_OK;
   if (!T_G_C || !out || n_views > kMaxViews) return COX_ERR_INVALID_ARG;
   for (u64 i = 0; i < n_views; ++i)
-    if (!all_finite(T_G_C + 7 * i, 7)) return COX_ERR_INVALID_ARG;
+    if (!finite_all(T_G_C + 7 * i, 7)) return COX_ERR_INVALID_ARG;
   COX_HIP(hipSetDevice(H->layer->device));
   COX_TRY(dev_grow(&H->d_poses, &H->poses_cap, 7 * n_views));
   COX_TRY(dev_grow(&H->d_out, &H->out_cap, n_views));
@@ -684,7 +636,7 @@ int cox_viewgain_evaluate_dev(cox_viewgain_t* H, const float* poses_dev, uint64_
 int cox_viewgain_visible(cox_viewgain_t* H, const float T_G_C[7], uint64_t cap, int32_t* voxel_xyz, uint8_t* cls, float* value, uint64_t* n) {
   COX_ENTRY();
   COX_TRY(device_present());
-  if (!H || !T_G_C || !n || !all_finite(T_G_C, 7)) return COX_ERR_INVALID_ARG;
+  if (!H || !T_G_C || !n || !finite_all(T_G_C, 7)) return COX_ERR_INVALID_ARG;
   COX_HIP(hipSetDevice(H->layer->device));
   COX_TRY(dev_grow(&H->d_poses, &H->poses_cap, 7));
   hipStream_t s = H->stream;
@@ -708,29 +660,18 @@ int cox_viewgain_visible(cox_viewgain_t* H, const float T_G_C[7], uint64_t cap, 
   if (cap < total) return COX_ERR_BUFFER_TOO_SMALL;
   // one staging allocation: xyz | value | cls
   const size_t b_xyz = voxel_xyz ? 12 * total : 0, b_val = value ? 4 * total : 0, b_cls = cls ? total : 0;
-  uint8_t* buf = nullptr;
-  {
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), b_xyz + b_val + b_cls);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      return e == hipErrorOutOfMemory ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-    }
-  }
-  int* d_xyz = voxel_xyz ? reinterpret_cast<int*>(buf) : nullptr;
-  float* d_val = value ? reinterpret_cast<float*>(buf + b_xyz) : nullptr;
-  uint8_t* d_cls = cls ? buf + b_xyz + b_val : nullptr;
+  DevBuf<uint8_t> buf;
+  COX_TRY(buf.alloc(b_xyz + b_val + b_cls));
+  int* d_xyz = voxel_xyz ? reinterpret_cast<int*>(buf.p) : nullptr;
+  float* d_val = value ? reinterpret_cast<float*>(buf.p + b_xyz) : nullptr;
+  uint8_t* d_cls = cls ? buf.p + b_xyz + b_val : nullptr;
   hipLaunchKernelGGL(k_vg_compact, dim3(1), dim3(kCompactThreads), 0, s, V, H->P, H->d_info, H->d_bitmap, static_cast<u64>(total), d_xyz, d_cls, d_val, d_n);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && voxel_xyz) e = hipMemcpyAsync(voxel_xyz, d_xyz, b_xyz, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess && value) e = hipMemcpyAsync(value, d_val, b_val, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess && cls) e = hipMemcpyAsync(cls, d_cls, b_cls, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(buf);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? COX_ERR_OUT_OF_MEMORY : COX_ERR_NO_DEVICE;
-  }
-  return COX_OK;
+  return cox_hip_status(e);
 }
 
 }  // extern "C"

@@ -153,6 +153,20 @@ def test_small_and_odd_images(hip, ref32, wh, scheme):
     assert len(idx) >= 1
 
 
+@pytest.mark.parametrize("colours", [(1, 1, 1), (0, 0, 0), (0, 1, 0)], ids=["rgba", "no-rgba", "rgba-for-the-large-one"])
+def test_image_sizes_small_large_small_on_one_integrator(hip, ref32, colours):
+    """The host entry keeps one staging buffer for depth and one for colour, which grow with the image and never shrink:
+    8 x 8, 64 x 48 and 8 x 8 through one integrator."""
+    layer, di, ref = pair(hip, ref32)
+    for i, ((w, h), colour) in enumerate(zip([(8, 8), (64, 48), (8, 8)], colours)):
+        K = dr.scaled_intrinsics(w, h)
+        _, T = dr.look_at([0.13 + 0.07 * i, -0.21, 0.17], [2.2, 0.1 * i, 0.05])
+        st = fuse(di, ref, T, dr.scene_depth(T, w, h, K), dr.scene_colors(w, h) if colour else None, K)
+        assert st["n_valid_pixels"] > 0 and st["n_updated_voxels"] > 0
+    idx, _ = same_layer(di, layer, ref)
+    assert len(idx) >= 1
+
+
 @pytest.mark.parametrize("K", [[39.0, 39.0, 80.0, 17.5], [39.0, 39.0, 23.5, -30.0], [39.0, 39.0, -15.0, 60.0]], ids=["right", "above", "corner"])
 def test_principal_point_outside_the_image(hip, ref32, K):
     K = np.array(K, np.float32)

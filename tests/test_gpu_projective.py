@@ -61,6 +61,20 @@ def test_depth_camera_stream_with_the_reference_sensor_model(hip, oracle, voxel)
         assert abs(rep["observed"] - want) <= (0.08 if const_w else 0.45) * want, (rep["observed"], want)
 
 
+def test_host_clouds_small_large_small_on_one_integrator(hip, oracle):
+    """The host entry keeps one staging buffer that grows with the cloud and never shrinks: 64, 4096 and 64 points through one
+    integrator, each frame's counters and the layer against the oracle."""
+    a, b = lidar_cloud(), lidar_cloud(wall_x=2.8)
+    pose = np.array([0.9990482, 0, 0, 0.0436194, 0.2, -0.1, 0.05], np.float32)
+    frames = [(IDENT, a[:64]), (pose, b[::6][:4096]), (IDENT, a[-64:])]
+    assert [len(p) for _, p in frames] == [64, 4096, 64]
+    (la, sa), (lb, sb) = run(hip, {}, 0.1, frames), run(oracle, {}, 0.1, frames)
+    compare_stats(sa, sb, keys=KEYS)
+    rep = compare_layers(la, lb, tol=0.0, check_color=False)
+    assert rep["bitexact_d"] and rep["bitexact_w"] and rep["observed"] > 1000, rep
+    assert all(s["n_updates"] > 0 for s in sb)
+
+
 def test_projective_layer_grows_and_async_device_path(hip, oracle):
     import torch
     frames = [(IDENT, lidar_cloud()), (IDENT, lidar_cloud(wall_x=2.5))]

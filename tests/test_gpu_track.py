@@ -264,6 +264,31 @@ def test_refine_dev_and_host_points_agree(hip, layers):
     assert none["status_name"] == "max_iterations" and none["iterations"] == 0 and np.array_equal(none["T_refined"], T0)
 
 
+def test_refine_host_points_small_large_small_on_one_tracker(hip, layers):
+    """cox_track_refine keeps one staging buffer that grows with the scan and never shrinks: 64, 4096 and 64 points through one
+    tracker.  One iteration each (nothing near a stop decision): the counts and the cost of the reference, and bit for bit the
+    pose a fresh tracker gets from the same points on the device."""
+    import torch
+    layer, ref = layers[("analytic", 0.10)]
+    T, pts = scan()
+    T0 = R.start_pose(T, 0.10, 6, 1.0, 2.0)
+    cfg = R.config(dof=6, max_iterations=1)
+    tr = Tracker(hip, layer, dof=6, max_iterations=1)
+    outs = []
+    for p in (pts[::4801][:64], pts[::75][:4096], pts[::4801][:64]):  # spread over the image: all three walls, full rank
+        got, exp = tr.refine(T0, p), ref.refine(T0, p, cfg)
+        assert got["status"] == exp["status"] == R.MAX_ITERATIONS and got["iterations"] == exp["iterations"] == 1
+        for key in ("first_n_used", "first_n_considered", "last_n_used", "last_n_considered"):
+            assert got[key] == exp[key], key
+        assert len(p) in (64, 4096) and exp["first_n_used"] >= 32 and abs(got["first_cost"] - exp["first_cost"]) <= len(p) * 2.0 ** -52 * exp["first_cost"]
+        dev_pts = torch.from_numpy(np.ascontiguousarray(p)).cuda()
+        torch.cuda.synchronize()
+        fresh = Tracker(hip, layer, dof=6, max_iterations=1).refine_dev(T0, dev_pts)
+        assert _same_bits(got["T"], fresh["T"]) and got["first_cost"] == fresh["first_cost"]
+        outs.append(got)
+    assert _same_bits(outs[0]["T"], outs[2]["T"]) and not _same_bits(outs[0]["T"], outs[1]["T"])
+
+
 # ---- edges ---------------------------------------------------------------------------------------------------------------------------------
 def test_lost_and_degenerate(hip, layers):
     T, pts = scan()

@@ -295,3 +295,30 @@ def test_cpp_pose_graph_with_a_registration_constraint_on_the_gpu(hip, tmp_path)
     out = subprocess.run([_build_posegraph_smoke(hip, tmp_path), "gpu"], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "registration" in out.stdout
+
+
+@pytest.fixture(scope="module")
+def hostutil_smoke(tmp_path_factory):
+    """tests/cpp/hostutil_smoke.cpp: coxgraph_amd/csrc/cox_host.hpp compiled on its own with hipcc, as the library's units see it."""
+    import shutil
+    hipcc = next((c for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc")) if c and os.path.exists(c)), None)
+    assert hipcc, "hipcc not found"
+    exe = str(tmp_path_factory.mktemp("hostutil") / "hostutil_smoke")
+    subprocess.check_call([hipcc, "-x", "hip", "-std=c++17", "--offload-arch=gfx950", "-Wall", "-Wextra", "-Werror", "-o", exe,
+                           os.path.join(ROOT, "tests", "cpp", "hostutil_smoke.cpp")])
+    return exe
+
+
+def test_host_helpers_without_a_device(hip, hostutil_smoke):
+    """Status mapping, COX_TRY, finite_all and no-op growth everywhere; where there is no device also the failure paths of
+    device_present, dev_alloc, dev_grow and DevBuf: the status, a null pointer, a capacity of 0 and no HIP error left behind."""
+    out = subprocess.run([hostutil_smoke], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert out.stdout.split() == ["device" if hip.device_count() > 0 else "no-device"]
+
+
+@pytest.mark.gpu
+def test_host_helpers_grow_on_the_gpu(hostutil_smoke):
+    """0 -> 16 -> 16 -> 17 -> 4 elements: a new buffer at the first and third step only, capacities 16, 16, 17, 17."""
+    out = subprocess.run([hostutil_smoke, "gpu"], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
