@@ -4,6 +4,10 @@ The binding is generic over (shared library, symbol prefix): the product engine 
 ``coxgraph_amd/lib/libcoxgraph_hip.so`` with prefix ``cox_``; the test suite loads its CPU checker
 (built from ``oracle/``, its own symbol prefix) through the same classes so parity tests read the
 same on both sides.  Nothing in this package loads that checker.
+
+The core comes first: ``Engine.call`` (look up, call, raise on a status), the argument helpers (``_ptr``, ``_stream``, ``_pose``,
+``_intrinsics``, ``_config`` ...) and ``_Handle``, the base of every class that owns an opaque C handle.  The classes after it
+only say which symbols they call with which arguments.
 """
 import ctypes as C
 import os
@@ -13,7 +17,7 @@ COX_OK = 0
 STATUS = {
     0: "COX_OK", -1: "COX_ERR_INVALID_ARG", -2: "COX_ERR_NO_DEVICE", -3: "COX_ERR_OUT_OF_MEMORY",
     -4: "COX_ERR_POOL_EXHAUSTED", -5: "COX_ERR_INDEX_RANGE", -6: "COX_ERR_UNSUPPORTED",
-    -7: "COX_ERR_BUFFER_TOO_SMALL", -8: "COX_ERR_INTERNAL",
+    -7: "COX_ERR_BUFFER_TOO_SMALL", -8: "COX_ERR_INTERNAL", -9: "COX_ERR_COMM",
 }
 METHODS = {"simple": 0, "merged": 1, "fast": 2, "projective": 3}
 QUERY_MODES = {"nearest": 0, "interpolate": 1, "adaptive": 2}  # cox_query_mode (include/coxgraph_hip_map.h)
@@ -76,8 +80,65 @@ class RegConfig(C.Structure):
     _fields_ = [("no_correspondence_cost", C.c_double)]
 
 
+# ---- the core: argument helpers, the engine, the handle base ---------------------------------------
 def _fp(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _opt(a):
+    """_fp of an optional host array."""
+    return None if a is None else _fp(a)
+
+
+def _ptr(t):
+    """A device buffer as c_void_p: a torch tensor (anything with data_ptr()), a raw address (int), or None."""
+    if t is None:
+        return None
+    return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+
+
+def _stream(s):
+    """A torch stream, a raw hipStream_t or None (the null stream) as c_void_p."""
+    return C.c_void_p(getattr(s, "cuda_stream", s) or 0)
+
+
+def _pose(T):
+    """A pose qw qx qy qz tx ty tz as contiguous float32 (7,)."""
+    T = np.ascontiguousarray(T, np.float32)
+    assert T.shape == (7,)
+    return T
+
+
+def _intrinsics(w, h, K):
+    """K = (fx, fy, cx, cy) as float32 (4,); None: synth.INTRINSICS[(w, h)]."""
+    if K is None:
+        from . import synth
+        K = synth.INTRINSICS[(w, h)]
+    K = np.ascontiguousarray(K, np.float32)
+    assert K.shape == (4,)
+    return K
+
+
+def _config(eng, Struct, default_symbol, overrides):
+    """Struct as default_symbol fills it, then the overrides: an unknown key raises AttributeError, a field that is an array
+    takes a sequence."""
+    c = Struct()
+    eng.fn(default_symbol, None)(C.byref(c))
+    for k, v in overrides.items():
+        if not hasattr(c, k):
+            raise AttributeError(k)
+        if isinstance(getattr(c, k), C.Array):
+            v = type(getattr(c, k))(*np.asarray(v).ravel().tolist())
+        setattr(c, k, v)
+    return c
+
+
+def _esdf_config(eng, max_distance_m=None, min_distance_m=None, default_distance_m=None, min_weight=None):
+    """cox_esdf_config_default with the fields given; default_distance_m follows max_distance_m when only that is given."""
+    if max_distance_m is not None and default_distance_m is None:
+        default_distance_m = max_distance_m
+    given = dict(max_distance_m=max_distance_m, min_distance_m=min_distance_m, default_distance_m=default_distance_m, min_weight=min_weight)
+    return _config(eng, EsdfConfig, "esdf_config_default", {k: v for k, v in given.items() if v is not None})
 
 
 class Engine:
@@ -89,6 +150,7 @@ class Engine:
         self.lib = C.CDLL(lib_path)
         self.prefix = prefix
         self.path = lib_path
+        self._status_fns = {}  # name -> bound function that returns a cox_status (call())
 
     def fn(self, name, restype=C.c_int):
         f = getattr(self.lib, self.prefix + name)
@@ -102,33 +164,73 @@ class Engine:
         if status != COX_OK:
             raise CoxError(status, what)
 
+    def call(self, name, *args):
+        """Look the symbol up, call it, raise CoxError(status, name) unless it returns COX_OK.  The bound function is kept: this is
+        the path of every per-frame call."""
+        try:
+            f = self._status_fns[name]
+        except KeyError:
+            f = self._status_fns[name] = self.lib[self.prefix + name]  # (an object of its own: fn() may set another restype on the shared one)
+            f.restype = C.c_int
+        status = f(*args)
+        if status != COX_OK:
+            raise CoxError(status, name)
+
     def default_config(self, **overrides):
-        cfg = TsdfConfig()
-        self.fn("tsdf_config_default", None)(C.byref(cfg))
-        for k, v in overrides.items():
-            if not hasattr(cfg, k):
-                raise AttributeError(k)
-            setattr(cfg, k, v)
-        return cfg
+        return _config(self, TsdfConfig, "tsdf_config_default", overrides)
 
     def device_count(self):
         return int(self.fn("device_count")()) if self.has("device_count") else 0
 
 
-class Layer:
-    """voxblox::Layer<TsdfVoxel> (cox_layer_t)."""
+class _Handle:
+    """What every owner of an opaque C handle shares: the engine, the handle, one idempotent close() and the guard in front of
+    every call.  The class-level defaults make close() and __del__ no-ops on an object whose constructor never reached the create
+    call."""
+    _destroy = None  # the symbol that frees the handle
+    _hattr = "h"     # the attribute that holds it
+    _borrows = ()    # attributes (layers, point sets) whose C objects the handle keeps raw pointers into
+    eng = None
+    h = None
 
-    def __init__(self, eng, voxel_size, voxels_per_side=16, device=0, capacity_blocks=0):
+    @classmethod
+    def _adopt(cls, eng, handle, **attrs):
+        """An object around an existing handle, without running __init__."""
+        self = cls.__new__(cls)
         self.eng = eng
-        self.voxel_size = float(voxel_size)
-        self.h = C.c_void_p()
-        eng.check(eng.fn("layer_create")(C.c_float(voxel_size), C.c_int(voxels_per_side), C.c_int(device),
-                                         C.c_uint64(capacity_blocks), C.byref(self.h)), "layer_create")
+        setattr(self, cls._hattr, handle)
+        for k, v in attrs.items():
+            setattr(self, k, v)
+        return self
+
+    def _guard(self, name):
+        """The handle, unless an object it points into was closed first: the C side would read freed memory."""
+        for a in self._borrows:
+            if not getattr(self, a).h:
+                raise CoxError(-1, name + " (the layer is closed)")
+        return getattr(self, self._hattr)
+
+    def _call(self, name, *args):
+        self.eng.call(name, self._guard(name), *args)
+
+    def _download(self, name, shapes, place=lambda arrays, cap: (*arrays, cap), query=None, also_ok=()):
+        """The two-call download: the first call, with no arrays and a capacity of 0, asks for the count n; the second fills one
+        zeroed array [n, *shape] per (shape, dtype) of `shapes`.  `place` puts the arrays and the capacity where the symbol takes them
+        between the handle and the count; `query` labels an error of the first call, `also_ok` are statuses it may return."""
+        h, f, n = self._guard(name), self.eng.fn(name), C.c_uint64()
+        status = f(h, *place([None] * len(shapes), C.c_uint64(0)), C.byref(n))
+        if status not in also_ok:
+            self.eng.check(status, query or name)
+        out = tuple(np.zeros((int(n.value), *shape), dtype) for shape, dtype in shapes)
+        if n.value:
+            self.eng.check(f(h, *place([_fp(a) for a in out], C.c_uint64(n.value)), C.byref(n)), name)
+        return out
 
     def close(self):
-        if self.h:
-            self.eng.fn("layer_destroy", None)(self.h)
-            self.h = C.c_void_p()
+        h = getattr(self, self._hattr)
+        if h:
+            self.eng.fn(self._destroy, None)(h)
+            setattr(self, self._hattr, C.c_void_p())
 
     def __del__(self):
         try:
@@ -136,78 +238,66 @@ class Layer:
         except Exception:
             pass
 
+
+class Layer(_Handle):
+    """voxblox::Layer<TsdfVoxel> (cox_layer_t)."""
+    _destroy = "layer_destroy"
+
+    def __init__(self, eng, voxel_size, voxels_per_side=16, device=0, capacity_blocks=0):
+        self.eng = eng
+        self.voxel_size = float(voxel_size)
+        self.h = C.c_void_p()
+        eng.call("layer_create", C.c_float(voxel_size), C.c_int(voxels_per_side), C.c_int(device), C.c_uint64(capacity_blocks), C.byref(self.h))
+
     def clear(self):  # removeAllBlocks
-        self.eng.check(self.eng.fn("layer_clear")(self.h), "layer_clear")
+        self._call("layer_clear")
 
     def stats(self):
         n, b = C.c_uint64(), C.c_uint64()
-        self.eng.check(self.eng.fn("layer_stats")(self.h, C.byref(n), C.byref(b)), "layer_stats")
+        self._call("layer_stats", C.byref(n), C.byref(b))
         return int(n.value), int(b.value)
 
     def download(self):
         """serializeLayerAsMsg: (block_idx int32[n,3], words uint32[n,4096,3]) sorted by (z,y,x)."""
-        n = C.c_uint64()
-        f = self.eng.fn("layer_download")
-        self.eng.check(f(self.h, None, None, C.c_uint64(0), C.byref(n)), "layer_download(query)")
-        nb = int(n.value)
-        idx = np.zeros((nb, 3), np.int32)
-        vox = np.zeros((nb, VOXELS_PER_BLOCK, 3), np.uint32)
-        if nb:
-            self.eng.check(f(self.h, _fp(idx), _fp(vox), C.c_uint64(nb), C.byref(n)), "layer_download")
-        return idx, vox
+        return self._download("layer_download", (((3,), np.int32), ((VOXELS_PER_BLOCK, 3), np.uint32)), query="layer_download(query)")
 
     def merge_from(self, other, T_B_A=None):
         """mergeLayerAintoLayerB(other, [T_B_A,] self)."""
-        T = None if T_B_A is None else np.ascontiguousarray(T_B_A, np.float32)
-        self.eng.check(self.eng.fn("layer_merge")(other.h, _fp(T) if T is not None else None, self.h), "layer_merge")
+        self.eng.call("layer_merge", other.h, None if T_B_A is None else _fp(_pose(T_B_A)), self.h)
 
     def registration_points(self, min_voxel_weight=1.0, max_voxel_distance=0.3):
         """finishSubmap()'s relevant voxels: float32 [n,5] = x, y, z, distance, weight."""
-        n = C.c_uint64()
-        f = self.eng.fn("layer_registration_points")
-        self.eng.check(f(self.h, C.c_float(min_voxel_weight), C.c_float(max_voxel_distance), None, C.c_uint64(0), C.byref(n)), "layer_registration_points")
-        out = np.zeros((int(n.value), 5), np.float32)
-        if n.value:
-            self.eng.check(f(self.h, C.c_float(min_voxel_weight), C.c_float(max_voxel_distance), _fp(out), C.c_uint64(n.value), C.byref(n)),
-                           "layer_registration_points")
-        return out
+        return self._download("layer_registration_points", (((5,), np.float32),),
+                              lambda a, cap: (C.c_float(min_voxel_weight), C.c_float(max_voxel_distance), *a, cap))[0]
 
     def surface_obb(self):
         """getSubmapFrameSurfaceObb -> (min[3], max[3], n_surface_voxels)."""
         mn, mx, n = np.zeros(3, np.float32), np.zeros(3, np.float32), C.c_uint64()
-        self.eng.check(self.eng.fn("layer_surface_obb")(self.h, _fp(mn), _fp(mx), C.byref(n)), "layer_surface_obb")
+        self._call("layer_surface_obb", _fp(mn), _fp(mx), C.byref(n))
         return mn, mx, int(n.value)
 
     def esdf(self, max_distance_m=None, min_distance_m=None, default_distance_m=None, min_weight=None):
         """generateEsdf(): a new layer (TSDF wire layout: distance = ESDF distance, weight = observed, colour word = fixed)."""
-        cfg = EsdfConfig()
-        self.eng.fn("esdf_config_default", None)(C.byref(cfg))
-        for k, v in (("max_distance_m", max_distance_m), ("min_distance_m", min_distance_m), ("default_distance_m", default_distance_m), ("min_weight", min_weight)):
-            if v is not None:
-                setattr(cfg, k, v)
-        if max_distance_m is not None and default_distance_m is None:
-            cfg.default_distance_m = max_distance_m
-        out = Layer.__new__(Layer)
-        out.eng, out.voxel_size, out.h = self.eng, self.voxel_size, C.c_void_p()
-        self.eng.check(self.eng.fn("esdf_from_tsdf")(self.h, C.byref(cfg), C.byref(out.h)), "esdf_from_tsdf")
+        cfg = _esdf_config(self.eng, max_distance_m, min_distance_m, default_distance_m, min_weight)
+        out = Layer._adopt(self.eng, C.c_void_p(), voxel_size=self.voxel_size)
+        self._call("esdf_from_tsdf", C.byref(cfg), C.byref(out.h))
         return out
 
     def reserve(self, capacity_blocks):
-        self.eng.check(self.eng.fn("layer_reserve")(self.h, C.c_uint64(capacity_blocks)), "layer_reserve")
+        self._call("layer_reserve", C.c_uint64(capacity_blocks))
 
     def capacity(self):
         n = C.c_uint64()
-        self.eng.check(self.eng.fn("layer_capacity")(self.h, C.byref(n)), "layer_capacity")
+        self._call("layer_capacity", C.byref(n))
         return int(n.value)
 
     def set_auto_grow(self, on):
-        self.eng.check(self.eng.fn("layer_set_auto_grow")(self.h, C.c_int(int(on))), "layer_set_auto_grow")
+        self._call("layer_set_auto_grow", C.c_int(int(on)))
 
     def clone_to_device(self, device, capacity_blocks=0):
         """Submap hand-over inside one process: block array + keys copied GPU to GPU, hash rebuilt on `device`."""
-        out = Layer.__new__(Layer)
-        out.eng, out.voxel_size, out.h = self.eng, self.voxel_size, C.c_void_p()
-        self.eng.check(self.eng.fn("layer_clone_to_device")(self.h, C.c_int(device), C.c_uint64(capacity_blocks), C.byref(out.h)), "layer_clone_to_device")
+        out = Layer._adopt(self.eng, C.c_void_p(), voxel_size=self.voxel_size)
+        self._call("layer_clone_to_device", C.c_int(device), C.c_uint64(capacity_blocks), C.byref(out.h))
         return out
 
     def n_blocks(self):
@@ -216,19 +306,18 @@ class Layer:
     def export_dev(self, idx_ptr, vox_ptr, cap_blocks):
         """serializeLayerAsMsg into device buffers (pointers as ints); returns the block count."""
         n = C.c_uint64()
-        self.eng.check(self.eng.fn("layer_export_dev")(self.h, C.c_void_p(idx_ptr), C.c_void_p(vox_ptr), C.c_uint64(cap_blocks), C.byref(n)), "layer_export_dev")
+        self._call("layer_export_dev", C.c_void_p(idx_ptr), C.c_void_p(vox_ptr), C.c_uint64(cap_blocks), C.byref(n))
         return int(n.value)
 
     def upload_dev(self, idx_ptr, vox_ptr, n_blocks, action=0):
         """deserializeMsgToLayer from device buffers (pointers as ints)."""
-        self.eng.check(self.eng.fn("layer_upload_dev")(self.h, C.c_void_p(idx_ptr), C.c_void_p(vox_ptr), C.c_uint64(n_blocks), C.c_int(action)), "layer_upload_dev")
+        self._call("layer_upload_dev", C.c_void_p(idx_ptr), C.c_void_p(vox_ptr), C.c_uint64(n_blocks), C.c_int(action))
 
     def upload(self, idx, vox, action=0):
         idx = np.ascontiguousarray(idx, np.int32)
         vox = np.ascontiguousarray(vox, np.uint32)
         assert vox.shape == (idx.shape[0], VOXELS_PER_BLOCK, 3)
-        self.eng.check(self.eng.fn("layer_upload")(self.h, _fp(idx), _fp(vox), C.c_uint64(idx.shape[0]), C.c_int(action)),
-                       "layer_upload")
+        self._call("layer_upload", _fp(idx), _fp(vox), C.c_uint64(idx.shape[0]), C.c_int(action))
 
     # ---- map queries (include/coxgraph_hip_map.h) ----
     def query(self, xyz, mode="interpolate", gradient=False):
@@ -240,41 +329,22 @@ class Layer:
         out = dict(distance=np.empty(n, np.float32), weight=np.empty(n, np.float32), status=np.empty(n, np.uint8))
         if gradient:
             out["gradient"] = np.empty((n, 3), np.float32)
-        self.eng.check(self.eng.fn("layer_query")(self.h, _fp(xyz), C.c_uint64(n), C.c_int(QUERY_MODES[mode]), C.c_int(int(gradient)),
-                                                  _fp(out["distance"]), _fp(out["weight"]), _fp(out["gradient"]) if gradient else None,
-                                                  _fp(out["status"])), "layer_query")
+        self._call("layer_query", _fp(xyz), C.c_uint64(n), C.c_int(QUERY_MODES[mode]), C.c_int(int(gradient)),
+                   _fp(out["distance"]), _fp(out["weight"]), _opt(out.get("gradient")), _fp(out["status"]))
         return out
 
     def query_dev(self, xyz, n=None, mode="interpolate", gradient=False, distance=None, weight=None, grad=None, status=None, stream=None):
         """cox_layer_query_dev: torch tensors on the layer's GPU or raw device pointers (ints; then n is required), enqueued on
         `stream` (a torch stream, a raw hipStream_t or None = the null stream), not waited for.  Outputs left as they were
         where a status bit is clear."""
-        def ptr(t):
-            if t is None:
-                return None
-            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
         if n is None:
             n = xyz.numel() // 3
-        s = getattr(stream, "cuda_stream", stream)
-        self.eng.check(self.eng.fn("layer_query_dev")(self.h, ptr(xyz), C.c_uint64(n), C.c_int(QUERY_MODES[mode]), C.c_int(int(gradient)), ptr(distance),
-                                                      ptr(weight), ptr(grad), ptr(status), C.c_void_p(s or 0)), "layer_query_dev")
+        self._call("layer_query_dev", _ptr(xyz), C.c_uint64(n), C.c_int(QUERY_MODES[mode]), C.c_int(int(gradient)), _ptr(distance),
+                   _ptr(weight), _ptr(grad), _ptr(status), _stream(stream))
 
     # ---- rendering (include/coxgraph_hip_render.h) ----
     def _render_args(self, T_G_C, w, h, K, cfg):
-        T = np.ascontiguousarray(T_G_C, np.float32)
-        assert T.shape == (7,)
-        if K is None:
-            from . import synth
-            K = synth.INTRINSICS[(w, h)]
-        K = np.ascontiguousarray(K, np.float32)
-        assert K.shape == (4,)
-        c = RenderConfig()
-        self.eng.fn("render_config_default", None)(C.byref(c))
-        for k, v in cfg.items():
-            if not hasattr(c, k):
-                raise AttributeError(k)
-            setattr(c, k, v)
-        return T, K, c
+        return _pose(T_G_C), _intrinsics(w, h, K), _config(self.eng, RenderConfig, "render_config_default", cfg)
 
     def render(self, T_G_C, w, h, K=None, **cfg):
         """Depth, normal and colour images of the layer seen from T_G_C through a w x h pinhole camera K = (fx, fy, cx, cy)
@@ -285,8 +355,8 @@ class Layer:
         out = dict(depth=np.empty((h, w), np.float32), normal=np.empty((h, w, 3), np.float32), rgba=np.empty((h, w, 4), np.uint8),
                    status=np.empty((h, w), np.uint8))
         st = RenderStats()
-        self.eng.check(self.eng.fn("layer_render")(self.h, _fp(T), C.c_int(w), C.c_int(h), _fp(K), C.byref(c), _fp(out["depth"]), _fp(out["normal"]),
-                                                   _fp(out["rgba"]), _fp(out["status"]), C.byref(st)), "layer_render")
+        self._call("layer_render", _fp(T), C.c_int(w), C.c_int(h), _fp(K), C.byref(c), _fp(out["depth"]), _fp(out["normal"]),
+                   _fp(out["rgba"]), _fp(out["status"]), C.byref(st))
         out["stats"] = st.asdict()
         return out
 
@@ -294,14 +364,9 @@ class Layer:
         """cox_layer_render_dev: outputs are torch tensors on the layer's GPU or raw device pointers (ints), any of them None;
         enqueued on `stream` (a torch stream, a raw hipStream_t or None = the null stream), not waited for.  Every pixel of
         every buffer given is written."""
-        def ptr(t):
-            if t is None:
-                return None
-            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
         T, K, c = self._render_args(T_G_C, w, h, K, cfg)
-        s = getattr(stream, "cuda_stream", stream)
-        self.eng.check(self.eng.fn("layer_render_dev")(self.h, _fp(T), C.c_int(w), C.c_int(h), _fp(K), C.byref(c), ptr(depth), ptr(normal), ptr(rgba),
-                                                       ptr(status), C.c_void_p(s or 0)), "layer_render_dev")
+        self._call("layer_render_dev", _fp(T), C.c_int(w), C.c_int(h), _fp(K), C.byref(c), _ptr(depth), _ptr(normal), _ptr(rgba),
+                   _ptr(status), _stream(stream))
 
     # ---- view gain (include/coxgraph_hip_gain.h) ----
     def view_gain(self, poses, **cfg):
@@ -334,107 +399,86 @@ class Layer:
     def free_points(self, min_distance):
         """createFreePointcloudFromEsdfLayer: (xyz float32[n,3] voxel centres, intensity float32[n] distances), blocks in download
         order, voxels in linear index order."""
-        f = self.eng.fn("layer_free_points")
-        n = C.c_uint64()
-        self.eng.check(f(self.h, C.c_float(min_distance), None, None, C.c_uint64(0), C.byref(n)), "layer_free_points(query)")
-        xyz = np.zeros((int(n.value), 3), np.float32)
-        inten = np.zeros(int(n.value), np.float32)
-        if n.value:
-            self.eng.check(f(self.h, C.c_float(min_distance), _fp(xyz), _fp(inten), C.c_uint64(n.value), C.byref(n)), "layer_free_points")
-        return xyz, inten
+        return self._download("layer_free_points", (((3,), np.float32), ((), np.float32)), lambda a, cap: (C.c_float(min_distance), *a, cap),
+                              query="layer_free_points(query)")
 
 
-class Integrator:
+class Integrator(_Handle):
     """voxblox::TsdfIntegratorBase (cox_integrator_t)."""
+    _destroy = "integrator_destroy"
+    _borrows = ("layer",)
 
     def __init__(self, eng, layer, cfg, method):
         self.eng, self.layer = eng, layer
         self.h = C.c_void_p()
         m = METHODS[method] if isinstance(method, str) else int(method)
-        eng.check(eng.fn("integrator_create")(layer.h, C.byref(cfg), C.c_int(m), C.byref(self.h)), "integrator_create")
-
-    def close(self):
-        if self.h:
-            self.eng.fn("integrator_destroy", None)(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        eng.call("integrator_create", layer.h, C.byref(cfg), C.c_int(m), C.byref(self.h))
 
     def integrate_points(self, T_G_C, xyz, rgba=None, freespace=False):
         """integratePointCloud(T_G_C, points_C, colors, freespace_points) with host buffers."""
-        T = np.ascontiguousarray(T_G_C, np.float32)
+        T = _pose(T_G_C)
         xyz = np.ascontiguousarray(xyz, np.float32)
-        assert T.shape == (7,) and xyz.ndim == 2 and xyz.shape[1] == 3
+        assert xyz.ndim == 2 and xyz.shape[1] == 3
         n = xyz.shape[0]
         if rgba is not None:
             rgba = np.ascontiguousarray(rgba, np.uint8)
             assert rgba.shape == (n, 4)
-        self.eng.check(self.eng.fn("integrate_points")(self.h, _fp(T), _fp(xyz), _fp(rgba) if rgba is not None else None,
-                                                       C.c_uint64(n), C.c_int(int(freespace))), "integrate_points")
+        self._call("integrate_points", _fp(T), _fp(xyz), _opt(rgba), C.c_uint64(n), C.c_int(int(freespace)))
 
     def deintegrate_points(self, T_G_C, xyz):
         """integratePointCloud(..., deintegrate = true): projective integrator only."""
-        T = np.ascontiguousarray(T_G_C, np.float32)
         xyz = np.ascontiguousarray(xyz, np.float32)
-        self.eng.check(self.eng.fn("integrate_points_ex")(self.h, _fp(T), _fp(xyz), None, C.c_uint64(xyz.shape[0]), C.c_int(0), C.c_int(1)), "integrate_points_ex")
+        self._call("integrate_points_ex", _fp(_pose(T_G_C)), _fp(xyz), None, C.c_uint64(xyz.shape[0]), C.c_int(0), C.c_int(1))
 
     def integrate_points_dev(self, T_G_C, xyz_ptr, rgba_ptr, n, freespace=False):
-        T = np.ascontiguousarray(T_G_C, np.float32)
-        self.eng.check(self.eng.fn("integrate_points_dev")(self.h, _fp(T), C.c_void_p(xyz_ptr), C.c_void_p(rgba_ptr or 0),
-                                                           C.c_uint64(n), C.c_int(int(freespace))), "integrate_points_dev")
+        self._call("integrate_points_dev", _fp(_pose(T_G_C)), C.c_void_p(xyz_ptr), C.c_void_p(rgba_ptr or 0),
+                   C.c_uint64(n), C.c_int(int(freespace)))
 
     def integrate_points_async(self, T_G_C, xyz_ptr, rgba_ptr, n, freespace=False):
         """Host buffers (addresses), frame not waited for; pinned buffers must stay untouched until wait_inputs() / sync()."""
-        T = np.ascontiguousarray(T_G_C, np.float32)
-        self.eng.check(self.eng.fn("integrate_points_async")(self.h, _fp(T), C.c_void_p(xyz_ptr), C.c_void_p(rgba_ptr or 0),
-                                                             C.c_uint64(n), C.c_int(int(freespace))), "integrate_points_async")
+        self._call("integrate_points_async", _fp(_pose(T_G_C)), C.c_void_p(xyz_ptr), C.c_void_p(rgba_ptr or 0),
+                   C.c_uint64(n), C.c_int(int(freespace)))
 
     def wait_inputs(self):
-        self.eng.check(self.eng.fn("integrator_wait_inputs")(self.h), "integrator_wait_inputs")
+        self._call("integrator_wait_inputs")
 
     def integrate_depth_dev(self, T_G_C, depth_ptr, rgba_ptr, w, h, K):
-        T = np.ascontiguousarray(T_G_C, np.float32)
         K = np.ascontiguousarray(K, np.float32)
-        self.eng.check(self.eng.fn("integrate_depth_dev")(self.h, _fp(T), C.c_void_p(depth_ptr), C.c_void_p(rgba_ptr or 0),
-                                                          C.c_int(w), C.c_int(h), _fp(K)), "integrate_depth_dev")
+        self._call("integrate_depth_dev", _fp(_pose(T_G_C)), C.c_void_p(depth_ptr), C.c_void_p(rgba_ptr or 0),
+                   C.c_int(w), C.c_int(h), _fp(K))
 
     def integrate_depth_async(self, T_G_C, depth_ptr, rgba_ptr, w, h, K):
         """Host depth / colour images (addresses), frame not waited for."""
-        T = np.ascontiguousarray(T_G_C, np.float32)
         K = np.ascontiguousarray(K, np.float32)
-        self.eng.check(self.eng.fn("integrate_depth_async")(self.h, _fp(T), C.c_void_p(depth_ptr), C.c_void_p(rgba_ptr or 0),
-                                                            C.c_int(w), C.c_int(h), _fp(K)), "integrate_depth_async")
+        self._call("integrate_depth_async", _fp(_pose(T_G_C)), C.c_void_p(depth_ptr), C.c_void_p(rgba_ptr or 0),
+                   C.c_int(w), C.c_int(h), _fp(K))
 
     def set_input_stream(self, stream_ptr, enable=True):
         """Order *_dev calls against the caller's HIP stream (e.g. torch.cuda.current_stream().cuda_stream)."""
-        self.eng.check(self.eng.fn("integrator_set_input_stream")(self.h, C.c_void_p(stream_ptr or 0), C.c_int(int(enable))), "integrator_set_input_stream")
+        self._call("integrator_set_input_stream", _stream(stream_ptr), C.c_int(int(enable)))
 
     def attach_history(self, obs):
         """cox_integrator_attach_history: every cloud fused from now on is also recorded in `obs` (an ObservationHistory) under
         its current frame id; None detaches."""
-        self.eng.check(self.eng.fn("integrator_attach_history")(self.h, obs.h if obs is not None else None), "integrator_attach_history")
+        self._call("integrator_attach_history", obs.h if obs is not None else None)
         self.history = obs  # (keeps the record alive while it is attached)
 
     def sync(self):
-        self.eng.check(self.eng.fn("integrator_sync")(self.h), "integrator_sync")
+        self._call("integrator_sync")
 
     def last_stats(self):
         s = FrameStats()
-        self.eng.check(self.eng.fn("integrator_last_stats")(self.h, C.byref(s)), "integrator_last_stats")
+        self._call("integrator_last_stats", C.byref(s))
         return s.asdict()
 
     def set_profiling(self, on=True):
         """0 / False = off, n >= 1 = HIP-event timing of the merge and apply kernels of every n-th frame."""
-        self.eng.check(self.eng.fn("integrator_set_profiling")(self.h, C.c_int(int(on))), "integrator_set_profiling")
+        self._call("integrator_set_profiling", C.c_int(int(on)))
 
     def stage_times(self, reset=False):
         """{'merge': (ms, launches), 'apply': (ms, launches)} measured with HIP events on the kernels' own streams."""
         ms, n = (C.c_double * 2)(), (C.c_uint64 * 2)()
-        self.eng.check(self.eng.fn("integrator_stage_times")(self.h, ms, n, C.c_int(int(reset))), "integrator_stage_times")
+        self._call("integrator_stage_times", ms, n, C.c_int(int(reset)))
         return {"merge": (float(ms[0]), int(n[0])), "apply": (float(ms[1]), int(n[1]))}
 
     KERNEL_CLASSES = ("merge", "apply", "bundle_hash", "point_sort", "touch_emit", "record_sort", "fast_start", "fast_visits", "fast_sweeps", "fast_round1")
@@ -443,141 +487,113 @@ class Integrator:
         """{class: (ms, regions)} for every kernel class of a frame (cox_kernel_class), HIP events on the kernels' own streams."""
         k = len(self.KERNEL_CLASSES)
         ms, n = (C.c_double * k)(), (C.c_uint64 * k)()
-        self.eng.check(self.eng.fn("integrator_class_times")(self.h, ms, n, C.c_int(int(reset))), "integrator_class_times")
+        self._call("integrator_class_times", ms, n, C.c_int(int(reset)))
         return {name: (float(ms[i]), int(n[i])) for i, name in enumerate(self.KERNEL_CLASSES)}
 
     def fast_stats(self):
         """method 'fast': run totals of the observed-set relaxation (cox_integrator_fast_stats)."""
         out = (C.c_uint64 * 10)()
-        self.eng.check(self.eng.fn("integrator_fast_stats")(self.h, out), "integrator_fast_stats")
+        self._call("integrator_fast_stats", out)
         return dict(sequential_frames=int(out[0]), round1_frames=int(out[1]), passes_round0=int(out[2]), passes_later_rounds=int(out[3]),
                     frames=int(out[4]), sequential_frames_list_outgrown=int(out[5]), sequential_frames_barrier_gave_up=int(out[6]), frames_with_three_rounds_or_more=int(out[7]), relax_work_ns=int(out[8]), relax_barrier_wait_ns=int(out[9]))
 
     def update_stats(self):
         """last frame: tiles whose classification was split over the chip, and their chunks (cox_integrator_update_stats)."""
         out = (C.c_uint64 * 2)()
-        self.eng.check(self.eng.fn("integrator_update_stats")(self.h, out), "integrator_update_stats")
+        self._call("integrator_update_stats", out)
         return dict(split_tiles=int(out[0]), chunks=int(out[1]))
 
     def host_time(self, reset=False):
         """(ms, frames): host time spent inside the integrate calls (enqueueing; cox_integrator_host_time)."""
         ms, n = C.c_double(), C.c_uint64()
-        self.eng.check(self.eng.fn("integrator_host_time")(self.h, C.byref(ms), C.byref(n), C.c_int(int(reset))), "integrator_host_time")
+        self._call("integrator_host_time", C.byref(ms), C.byref(n), C.c_int(int(reset)))
         return float(ms.value), int(n.value)
 
     def kernel_time(self, reset=False):
         ms, n = C.c_double(), C.c_uint64()
-        self.eng.check(self.eng.fn("integrator_kernel_time")(self.h, C.byref(ms), C.byref(n), C.c_int(int(reset))),
-                       "integrator_kernel_time")
+        self._call("integrator_kernel_time", C.byref(ms), C.byref(n), C.c_int(int(reset)))
         return float(ms.value), int(n.value)
 
 
-class ObservationHistory:
+class ObservationHistory(_Handle):
     """Which frames saw which part of a submap (cox_obs_t, include/coxgraph_hip_history.h): per 16^3 block 64 cells of 4x4x4
     voxels, per cell a 256-bit mask of frame ids."""
+    _destroy = "obs_destroy"
     CELLS, WORDS = 64, 8
 
     def __init__(self, eng, layer, capacity_blocks=0):
         self.eng, self.voxel_size = eng, layer.voxel_size
         self.h = C.c_void_p()
-        eng.check(eng.fn("obs_create")(layer.h, C.c_uint64(capacity_blocks), C.byref(self.h)), "obs_create")
-
-    def close(self):
-        if self.h:
-            self.eng.fn("obs_destroy", None)(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        eng.call("obs_create", layer.h, C.c_uint64(capacity_blocks), C.byref(self.h))
 
     def clear(self):
-        self.eng.check(self.eng.fn("obs_clear")(self.h), "obs_clear")
+        self._call("obs_clear")
 
     def set_auto_grow(self, on):
-        self.eng.check(self.eng.fn("obs_set_auto_grow")(self.h, C.c_int(int(on))), "obs_set_auto_grow")
+        self._call("obs_set_auto_grow", C.c_int(int(on)))
 
     def set_frame(self, frame_id):
         """The id (0..255) under which clouds are recorded until it is changed."""
-        self.eng.check(self.eng.fn("obs_set_frame")(self.h, C.c_uint32(int(frame_id))), "obs_set_frame")
+        self._call("obs_set_frame", C.c_uint32(int(frame_id)))
 
     def record(self, T_G_C, xyz, min_ray, max_ray, freespace=False, allow_clear=True):
         """Record one host cloud (points in the sensor frame); returns when it is recorded."""
-        T = np.ascontiguousarray(T_G_C, np.float32)
         xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        self.eng.check(self.eng.fn("obs_record")(self.h, _fp(T), _fp(xyz), C.c_uint64(len(xyz)), C.c_int(int(freespace)), C.c_float(min_ray),
-                                                 C.c_float(max_ray), C.c_int(int(allow_clear))), "obs_record")
+        self._call("obs_record", _fp(_pose(T_G_C)), _fp(xyz), C.c_uint64(len(xyz)), C.c_int(int(freespace)), C.c_float(min_ray),
+                   C.c_float(max_ray), C.c_int(int(allow_clear)))
 
     def record_dev(self, T_G_C, xyz, min_ray, max_ray, n=None, freespace=False, allow_clear=True, stream=None):
         """cox_obs_record_dev: xyz a torch tensor on the record's GPU or a raw device pointer (int; then n is required), ordered
         against `stream` (a torch stream, a raw hipStream_t or None = the null stream); not waited for."""
-        T = np.ascontiguousarray(T_G_C, np.float32)
         if n is None:
             n = xyz.numel() // 3
-        ptr = xyz.data_ptr() if hasattr(xyz, "data_ptr") else int(xyz)
-        s = getattr(stream, "cuda_stream", stream)
-        self.eng.check(self.eng.fn("obs_record_dev")(self.h, _fp(T), C.c_void_p(ptr), C.c_uint64(n), C.c_int(int(freespace)), C.c_float(min_ray),
-                                                     C.c_float(max_ray), C.c_int(int(allow_clear)), C.c_void_p(s or 0)), "obs_record_dev")
+        self._call("obs_record_dev", _fp(_pose(T_G_C)), _ptr(xyz), C.c_uint64(n), C.c_int(int(freespace)), C.c_float(min_ray),
+                   C.c_float(max_ray), C.c_int(int(allow_clear)), _stream(stream))
 
     def sync(self):
         """Wait for the records; raises CoxError (COX_ERR_POOL_EXHAUSTED ...) when marks were lost since the last call."""
-        self.eng.check(self.eng.fn("obs_sync")(self.h), "obs_sync")
+        self._call("obs_sync")
 
     def stats(self):
         """dict(blocks, marked_cells, bytes)."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self.eng.check(self.eng.fn("obs_stats")(self.h, C.byref(a), C.byref(b), C.byref(c)), "obs_stats")
+        self._call("obs_stats", C.byref(a), C.byref(b), C.byref(c))
         return dict(blocks=int(a.value), marked_cells=int(b.value), bytes=int(c.value))
 
     def counts(self):
         """Running totals: (points that marked, atomic ORs left after the lanes of a wave that share a cell merged)."""
         a, b = C.c_uint64(), C.c_uint64()
-        self.eng.check(self.eng.fn("obs_counts")(self.h, C.byref(a), C.byref(b)), "obs_counts")
+        self._call("obs_counts", C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
     def download(self):
         """(block_index int32[n,3] in (z, y, x) order, masks uint32[n,64,8])."""
-        n = C.c_uint64()
-        f = self.eng.fn("obs_download")
-        self.eng.check(f(self.h, None, None, C.c_uint64(0), C.byref(n)), "obs_download(query)")
-        nb = int(n.value)
-        idx = np.zeros((nb, 3), np.int32)
-        masks = np.zeros((nb, self.CELLS, self.WORDS), np.uint32)
-        if nb:
-            self.eng.check(f(self.h, _fp(idx), _fp(masks), C.c_uint64(nb), C.byref(n)), "obs_download")
-        return idx, masks
+        return self._download("obs_download", (((3,), np.int32), ((self.CELLS, self.WORDS), np.uint32)), query="obs_download(query)")
 
 
-class RegPoints:
+class RegPoints(_Handle):
+    _destroy = "regpoints_destroy"
+
     def __init__(self, eng, pts, device=0):
         self.eng = eng
         pts = np.ascontiguousarray(pts, np.float32)
         assert pts.ndim == 2 and pts.shape[1] == 5
         self.n = pts.shape[0]
         self.h = C.c_void_p()
-        eng.check(eng.fn("regpoints_create")(C.c_int(device), _fp(pts), C.c_uint64(self.n), C.byref(self.h)), "regpoints_create")
+        eng.call("regpoints_create", C.c_int(device), _fp(pts), C.c_uint64(self.n), C.byref(self.h))
 
     @classmethod
     def from_layer(cls, eng, layer, min_voxel_weight=1.0, max_voxel_distance=0.3):
         """finishSubmap()'s relevant-voxel set, built and kept on the engine's side (no host round trip)."""
-        self = cls.__new__(cls)
-        self.eng = eng
-        self.h = C.c_void_p()
-        eng.check(eng.fn("regpoints_from_layer")(layer.h, C.c_float(min_voxel_weight), C.c_float(max_voxel_distance), C.byref(self.h)),
-                  "regpoints_from_layer")
-        n = C.c_uint64()
-        eng.check(eng.fn("regpoints_size")(self.h, C.byref(n)), "regpoints_size")
-        self.n = int(n.value)
-        return self
+        h = C.c_void_p()
+        eng.call("regpoints_from_layer", layer.h, C.c_float(min_voxel_weight), C.c_float(max_voxel_distance), C.byref(h))
+        return cls._wrap(eng, h)
 
     @classmethod
     def _wrap(cls, eng, h):
-        self = cls.__new__(cls)
-        self.eng, self.h = eng, h
+        self = cls._adopt(eng, h)
         n = C.c_uint64()
-        eng.check(eng.fn("regpoints_size")(self.h, C.byref(n)), "regpoints_size")
+        self._call("regpoints_size", C.byref(n))
         self.n = int(n.value)
         return self
 
@@ -585,7 +601,7 @@ class RegPoints:
     def from_device(cls, eng, ptr, n, device=0):
         """A set whose n*5 floats already sit in HBM (pointer as int)."""
         h = C.c_void_p()
-        eng.check(eng.fn("regpoints_create_dev")(C.c_int(device), C.c_void_p(ptr), C.c_uint64(n), C.byref(h)), "regpoints_create_dev")
+        eng.call("regpoints_create_dev", C.c_int(device), C.c_void_p(ptr), C.c_uint64(n), C.byref(h))
         return cls._wrap(eng, h)
 
     @classmethod
@@ -593,58 +609,38 @@ class RegPoints:
         """finishSubmap()'s isosurface vertices (the "explicit" set), built and kept on the engine's side."""
         thr = 0.5 * layer.voxel_size if vertex_proximity_threshold is None else vertex_proximity_threshold
         h, nm, nc = C.c_void_p(), C.c_uint64(), C.c_uint64()
-        eng.check(eng.fn("regpoints_from_isosurface")(layer.h, C.c_float(min_weight), C.c_float(thr), C.byref(h), C.byref(nm), C.byref(nc)), "regpoints_from_isosurface")
+        eng.call("regpoints_from_isosurface", layer.h, C.c_float(min_weight), C.c_float(thr), C.byref(h), C.byref(nm), C.byref(nc))
         self = cls._wrap(eng, h)
         self.n_mesh_vertices, self.n_connected_vertices = int(nm.value), int(nc.value)
         return self
 
     def clone_to_device(self, device):
         h = C.c_void_p()
-        self.eng.check(self.eng.fn("regpoints_clone_to_device")(self.h, C.c_int(device), C.byref(h)), "regpoints_clone_to_device")
+        self._call("regpoints_clone_to_device", C.c_int(device), C.byref(h))
         return RegPoints._wrap(self.eng, h)
 
     def data_ptr(self):
         p, n = C.c_void_p(), C.c_uint64()
-        self.eng.check(self.eng.fn("regpoints_data_dev")(self.h, C.byref(p), C.byref(n)), "regpoints_data_dev")
+        self._call("regpoints_data_dev", C.byref(p), C.byref(n))
         return int(p.value or 0), int(n.value)
 
     def download(self):
         out = np.zeros((self.n, 5), np.float32)
         n = C.c_uint64()
-        self.eng.check(self.eng.fn("regpoints_download")(self.h, _fp(out), C.c_uint64(self.n), C.byref(n)), "regpoints_download")
+        self._call("regpoints_download", _fp(out), C.c_uint64(self.n), C.byref(n))
         return out
 
-    def close(self):
-        if self.h:
-            self.eng.fn("regpoints_destroy", None)(self.h)
-            self.h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Registration:
+class Registration(_Handle):
     """voxgraph::RegistrationCostFunction for one (reference points, reading layer) pair."""
+    _destroy = "reg_destroy"
+    _borrows = ("ref", "reading")
 
     def __init__(self, eng, ref_points, reading_layer, no_correspondence_cost=0.0):
         self.eng, self.ref, self.reading = eng, ref_points, reading_layer
         cfg = RegConfig(no_correspondence_cost)
         self.h = C.c_void_p()
-        eng.check(eng.fn("reg_create")(ref_points.h, reading_layer.h, C.byref(cfg), C.byref(self.h)), "reg_create")
-
-    def close(self):
-        if self.h:
-            self.eng.fn("reg_destroy", None)(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        eng.call("reg_create", ref_points.h, reading_layer.h, C.byref(cfg), C.byref(self.h))
 
     def _args(self, pose_ref, pose_read, sample_idx):
         pr = np.ascontiguousarray(pose_ref, np.float64)
@@ -661,9 +657,7 @@ class Registration:
         r = np.zeros(n, np.float64)
         jf = np.zeros((n, 4), np.float64) if jacobians else None
         jr = np.zeros((n, 4), np.float64) if jacobians else None
-        self.eng.check(self.eng.fn("reg_evaluate")(self.h, _fp(pr), _fp(pd), _fp(si) if si is not None else None, C.c_uint64(n),
-                                                   _fp(r), _fp(jf) if jacobians else None, _fp(jr) if jacobians else None),
-                       "reg_evaluate")
+        self._call("reg_evaluate", _fp(pr), _fp(pd), _opt(si), C.c_uint64(n), _fp(r), _opt(jf), _opt(jr))
         return r, jf, jr
 
     def normal_eq(self, pose_ref, pose_read, sample_idx=None):
@@ -671,48 +665,41 @@ class Registration:
         H = np.zeros((8, 8), np.float64)
         b = np.zeros(8, np.float64)
         cost, nc = C.c_double(), C.c_uint64()
-        self.eng.check(self.eng.fn("reg_normal_eq")(self.h, _fp(pr), _fp(pd), _fp(si) if si is not None else None, C.c_uint64(n),
-                                                    _fp(H), _fp(b), C.byref(cost), C.byref(nc)), "reg_normal_eq")
+        self._call("reg_normal_eq", _fp(pr), _fp(pd), _opt(si), C.c_uint64(n), _fp(H), _fp(b), C.byref(cost), C.byref(nc))
         return H, b, float(cost.value), int(nc.value)
 
     def set_samples(self, sample_idx):
         """Keep the sample indices on the engine's side; later calls pass sample_idx=None and use them."""
         if sample_idx is None:
-            self.eng.check(self.eng.fn("reg_set_samples")(self.h, None, C.c_uint64(0)), "reg_set_samples")
+            self._call("reg_set_samples", None, C.c_uint64(0))
             self.stored_n = None
             return
         si = np.ascontiguousarray(sample_idx, np.uint32)
-        self.eng.check(self.eng.fn("reg_set_samples")(self.h, _fp(si), C.c_uint64(si.shape[0])), "reg_set_samples")
+        self._call("reg_set_samples", _fp(si), C.c_uint64(si.shape[0]))
         self.stored_n = int(si.shape[0])
 
     def draw_samples(self, n_res, seed):
         """The weighted sampler's draws for one evaluation, made on the engine's side; they become the stored set."""
-        self.eng.check(self.eng.fn("reg_draw_samples")(self.h, C.c_uint64(n_res), C.c_uint64(seed)), "reg_draw_samples")
+        self._call("reg_draw_samples", C.c_uint64(n_res), C.c_uint64(seed))
         self.stored_n = int(n_res)
 
     def get_samples(self):
-        n = C.c_uint64()
-        f = self.eng.fn("reg_get_samples")
-        self.eng.check(f(self.h, None, C.c_uint64(0), C.byref(n)), "reg_get_samples")
-        out = np.zeros(int(n.value), np.uint32)
-        if n.value:
-            self.eng.check(f(self.h, _fp(out), C.c_uint64(n.value), C.byref(n)), "reg_get_samples")
-        return out
+        return self._download("reg_get_samples", (((), np.uint32),))[0]
 
     def normal_eq_begin(self, pose_ref, pose_read, sample_idx=None):
         pr, pd, si, n = self._args(pose_ref, pose_read, sample_idx)
-        self.eng.check(self.eng.fn("reg_normal_eq_begin")(self.h, _fp(pr), _fp(pd), _fp(si) if si is not None else None, C.c_uint64(n)), "reg_normal_eq_begin")
+        self._call("reg_normal_eq_begin", _fp(pr), _fp(pd), _opt(si), C.c_uint64(n))
 
     def normal_eq_finish(self):
         H = np.zeros((8, 8), np.float64)
         b = np.zeros(8, np.float64)
         cost, nc = C.c_double(), C.c_uint64()
-        self.eng.check(self.eng.fn("reg_normal_eq_finish")(self.h, _fp(H), _fp(b), C.byref(cost), C.byref(nc)), "reg_normal_eq_finish")
+        self._call("reg_normal_eq_finish", _fp(H), _fp(b), C.byref(cost), C.byref(nc))
         return H, b, float(cost.value), int(nc.value)
 
     def kernel_time(self, reset=False):
         ms, n = C.c_double(), C.c_uint64()
-        self.eng.check(self.eng.fn("reg_kernel_time")(self.h, C.byref(ms), C.byref(n), C.c_int(int(reset))), "reg_kernel_time")
+        self._call("reg_kernel_time", C.byref(ms), C.byref(n), C.c_int(int(reset)))
         return float(ms.value), int(n.value)
 
     @staticmethod
@@ -721,54 +708,43 @@ class Registration:
         samples, or all its points).  -> [(H 8x8, b 8, cost, n_corr)] in the order of `regs`."""
         n = len(regs)
         eng = regs[0].eng
-        handles = (C.c_void_p * n)(*[r.h for r in regs])
+        handles = (C.c_void_p * n)(*[r._guard("reg_normal_eq_batch") for r in regs])
         pr = np.ascontiguousarray(poses_ref, np.float64).reshape(n, 4)
         pd = np.ascontiguousarray(poses_read, np.float64).reshape(n, 4)
         H = np.zeros((n, 8, 8), np.float64)
         b = np.zeros((n, 8), np.float64)
         cost = np.zeros(n, np.float64)
         nc = np.zeros(n, np.uint64)
-        eng.check(eng.fn("reg_normal_eq_batch")(handles, C.c_uint64(n), _fp(pr), _fp(pd), _fp(H), _fp(b), _fp(cost), _fp(nc)), "reg_normal_eq_batch")
+        eng.call("reg_normal_eq_batch", handles, C.c_uint64(n), _fp(pr), _fp(pd), _fp(H), _fp(b), _fp(cost), _fp(nc))
         return [(H[c], b[c], float(cost[c]), int(nc[c])) for c in range(n)]
 
 
-class Comm:
+class Comm(_Handle):
     """cox_comm_t: RCCL behind the C ABI (one rank = one process = one GPU) -- the collectives the C++ host uses."""
+    _destroy = "comm_destroy"
     ID_BYTES = 128
 
     @staticmethod
     def unique_id(eng):
         buf = (C.c_uint8 * Comm.ID_BYTES)()
-        eng.check(eng.fn("comm_unique_id")(buf), "comm_unique_id")
+        eng.call("comm_unique_id", buf)
         return bytes(buf)
 
     def __init__(self, eng, device, rank, world, unique_id):
         self.eng = eng
         self.h = C.c_void_p()
         buf = (C.c_uint8 * Comm.ID_BYTES).from_buffer_copy(unique_id)
-        eng.check(eng.fn("comm_init_rank")(C.c_int(device), C.c_int(rank), C.c_int(world), buf, C.byref(self.h)), "comm_init_rank")
+        eng.call("comm_init_rank", C.c_int(device), C.c_int(rank), C.c_int(world), buf, C.byref(self.h))
         self.rank, self.world = rank, world
-
-    def close(self):
-        if self.h:
-            self.eng.fn("comm_destroy", None)(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def allreduce_f64(self, buf):
         """in-place sum over the ranks of a float64 numpy array (host in, host out)"""
         a = np.ascontiguousarray(buf, np.float64)
-        self.eng.check(self.eng.fn("comm_allreduce_f64")(self.h, _fp(a), C.c_uint64(a.size)), "comm_allreduce_f64")
+        self._call("comm_allreduce_f64", _fp(a), C.c_uint64(a.size))
         return a
 
     def allgather_dev(self, send_ptr, recv_ptr, bytes_per_rank, producer_stream=0):
-        self.eng.check(self.eng.fn("comm_allgather_dev_on")(self.h, C.c_void_p(send_ptr), C.c_void_p(recv_ptr), C.c_uint64(bytes_per_rank),
-                                                            C.c_void_p(producer_stream or 0)), "comm_allgather_dev_on")
+        self._call("comm_allgather_dev_on", C.c_void_p(send_ptr), C.c_void_p(recv_ptr), C.c_uint64(bytes_per_rank), _stream(producer_stream))
 
 
 class MeshMsgStruct(C.Structure):
@@ -821,44 +797,27 @@ class MeshMsg:
         return m
 
 
-class MeshConverter:
+class MeshConverter(_Handle):
     """voxblox::MeshConverter (cox_meshconv_t): recover mode's mesh -> per-pose point clouds."""
+    _destroy = "meshconv_destroy"
 
     def __init__(self, eng, interpolate_voxel_size=0.2, device=0):
         self.eng = eng
         self.h = C.c_void_p()
-        eng.check(eng.fn("meshconv_create")(C.c_int(device), C.c_float(interpolate_voxel_size), C.byref(self.h)), "meshconv_create")
-
-    def close(self):
-        if self.h:
-            self.eng.fn("meshconv_destroy", None)(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        eng.call("meshconv_create", C.c_int(device), C.c_float(interpolate_voxel_size), C.byref(self.h))
 
     def set_mesh(self, mesh):
         m = mesh.struct()
-        self.eng.check(self.eng.fn("meshconv_set_mesh")(self.h, C.byref(m)), "meshconv_set_mesh")
+        self._call("meshconv_set_mesh", C.byref(m))
 
     def convert(self):
         """convertToPointCloud -> (converted?, recovered xyz float32[n,3], recovered rgb uint8[n,3])."""
         n, ok = C.c_uint64(), C.c_int()
-        self.eng.check(self.eng.fn("meshconv_convert")(self.h, C.byref(n), C.byref(ok)), "meshconv_convert")
+        self._call("meshconv_convert", C.byref(n), C.byref(ok))
         return bool(ok.value), *self.recovered()
 
     def recovered(self):
-        n = C.c_uint64()
-        f = self.eng.fn("meshconv_recovered")
-        self.eng.check(f(self.h, None, None, C.c_uint64(0), C.byref(n)), "meshconv_recovered(query)")
-        xyz = np.zeros((int(n.value), 3), np.float32)
-        rgb = np.zeros((int(n.value), 3), np.uint8)
-        if n.value:
-            self.eng.check(f(self.h, _fp(xyz), _fp(rgb), C.c_uint64(n.value), C.byref(n)), "meshconv_recovered")
-        return xyz, rgb
+        return self._download("meshconv_recovered", (((3,), np.float32), ((3,), np.uint8)), query="meshconv_recovered(query)")
 
     def pose_clouds(self):
         """The sequence getNextPointcloud yields: list of (T_G_C float32[7], points_C float32[n,3], colors uint8[n,4])."""
@@ -866,42 +825,42 @@ class MeshConverter:
         i = C.c_int32(0)
         T = np.zeros(7, np.float32)
         n, more = C.c_uint64(), C.c_int()
-        nxt, dl = self.eng.fn("meshconv_next"), self.eng.fn("meshconv_download")
         while True:
             k = int(i.value)
             px, pc = C.c_void_p(), C.c_void_p()
-            self.eng.check(nxt(self.h, C.byref(i), _fp(T), C.byref(px), C.byref(pc), C.byref(n), C.byref(more)), "meshconv_next")
+            self._call("meshconv_next", C.byref(i), _fp(T), C.byref(px), C.byref(pc), C.byref(n), C.byref(more))
             if not more.value:
                 break
             xyz = np.zeros((int(n.value), 3), np.float32)
             rgba = np.zeros((int(n.value), 4), np.uint8)
             if n.value:
-                self.eng.check(dl(self.h, C.c_int32(k), _fp(xyz), _fp(rgba), C.c_uint64(n.value), C.byref(n)), "meshconv_download")
+                self._call("meshconv_download", C.c_int32(k), _fp(xyz), _fp(rgba), C.c_uint64(n.value), C.byref(n))
             out.append((T.copy(), xyz, rgba))
         return out
 
     def clear(self):
-        self.eng.check(self.eng.fn("meshconv_clear")(self.h), "meshconv_clear")
+        self._call("meshconv_clear")
 
     def process_mesh(self, integrator, mesh):
         """TsdfRecover::processMesh up to the serialisation: -> (n_recovered_points, n_integratePointCloud_calls)."""
         m = mesh.struct()
         nr, ni = C.c_uint64(), C.c_uint64()
-        self.eng.check(self.eng.fn("recover_process_mesh")(self.h, integrator.h, C.byref(m), C.byref(nr), C.byref(ni)), "recover_process_mesh")
+        self._call("recover_process_mesh", integrator._guard("recover_process_mesh"), C.byref(m), C.byref(nr), C.byref(ni))
         return int(nr.value), int(ni.value)
 
 
 COLOR_MODES = {"color": 0, "normals": 1, "gray": 2, "lambert": 3, "lambert_color": 4}
 
 
-class MeshLayer:
+class MeshLayer(_Handle):
     """voxblox::MeshLayer of a TSDF layer (cox_meshlayer_t, include/coxgraph_hip_mesh.h): per block with triangles its index and
     vertex range; per vertex position, face normal and colour; triangle t = vertices 3t, 3t+1, 3t+2."""
+    _destroy = "meshlayer_destroy"
 
     def __init__(self, eng, h):
         self.eng, self.h = eng, h
         nb, nv, edge = C.c_uint64(), C.c_uint64(), C.c_float()
-        eng.check(eng.fn("meshlayer_size")(self.h, C.byref(nb), C.byref(nv), C.byref(edge)), "meshlayer_size")
+        self._call("meshlayer_size", C.byref(nb), C.byref(nv), C.byref(edge))
         self.n_blocks, self.n_vertices, self.block_edge_length = int(nb.value), int(nv.value), float(edge.value)
         self.n_triangles = self.n_vertices // 3
 
@@ -909,24 +868,13 @@ class MeshLayer:
     def from_layer(cls, eng, layer, min_weight=1e-4):
         """MeshIntegrator::generateMesh over the whole layer (corners valid when weight > min_weight)."""
         h = C.c_void_p()
-        eng.check(eng.fn("meshlayer_from_layer")(layer.h, C.c_float(min_weight), C.byref(h), None, None), "meshlayer_from_layer")
+        eng.call("meshlayer_from_layer", layer.h, C.c_float(min_weight), C.byref(h), None, None)
         return cls(eng, h)
-
-    def close(self):
-        if self.h:
-            self.eng.fn("meshlayer_destroy", None)(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def stats(self):
         """(vertices whose colour voxel lay in no block, (count kernel ms, write kernel ms))."""
         n, ms = C.c_uint64(), np.zeros(2, np.float64)
-        self.eng.check(self.eng.fn("meshlayer_stats")(self.h, C.byref(n), _fp(ms)), "meshlayer_stats")
+        self._call("meshlayer_stats", C.byref(n), _fp(ms))
         return int(n.value), (float(ms[0]), float(ms[1]))
 
     def download(self):
@@ -934,40 +882,37 @@ class MeshLayer:
         nb, nv = self.n_blocks, self.n_vertices
         out = dict(block_index=np.zeros((nb, 3), np.int32), vertex_begin=np.zeros(nb + 1, np.uint64), xyz=np.zeros((nv, 3), np.float32),
                    normals=np.zeros((nv, 3), np.float32), rgb=np.zeros((nv, 3), np.uint8))
-        self.eng.check(self.eng.fn("meshlayer_download")(self.h, *[_fp(out[k]) for k in ("block_index", "vertex_begin", "xyz", "normals", "rgb")],
-                                                         C.c_uint64(nb), C.c_uint64(nv)), "meshlayer_download")
+        self._call("meshlayer_download", *[_fp(out[k]) for k in ("block_index", "vertex_begin", "xyz", "normals", "rgb")],
+                   C.c_uint64(nb), C.c_uint64(nv))
         return out
 
     def data_ptr(self):
         """(xyz, normals, rgb) device pointers as ints, and the vertex count."""
         p, q, r, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
-        self.eng.check(self.eng.fn("meshlayer_data_dev")(self.h, C.byref(p), C.byref(q), C.byref(r), C.byref(n)), "meshlayer_data_dev")
+        self._call("meshlayer_data_dev", C.byref(p), C.byref(q), C.byref(r), C.byref(n))
         return int(p.value or 0), int(q.value or 0), int(r.value or 0), int(n.value)
 
     def transform(self, T):
         """In place: positions T p, normals R n (T = qw qx qy qz tx ty tz)."""
-        T = np.ascontiguousarray(T, np.float32)
-        assert T.shape == (7,)
-        self.eng.check(self.eng.fn("meshlayer_transform")(self.h, _fp(T)), "meshlayer_transform")
+        self._call("meshlayer_transform", _fp(_pose(T)))
 
     def msg_arrays(self, color_mode="color"):
         """generateVoxbloxMeshMsg's per-vertex arrays: dict(x, y, z uint16[nv], r, g, b uint8[nv])."""
         nv = self.n_vertices
         out = {k: np.zeros(nv, np.uint16) for k in "xyz"}
         out.update({k: np.zeros(nv, np.uint8) for k in "rgb"})
-        self.eng.check(self.eng.fn("meshlayer_msg")(self.h, C.c_int(COLOR_MODES[color_mode]), *[_fp(out[k]) for k in "xyzrgb"], C.c_uint64(nv)),
-                       "meshlayer_msg")
+        self._call("meshlayer_msg", C.c_int(COLOR_MODES[color_mode]), *[_fp(out[k]) for k in "xyzrgb"], C.c_uint64(nv))
         return out
 
     def history(self, obs, with_time=False):
         """cox_meshlayer_history against an ObservationHistory: dict(history_begin uint64[nt + 1], history uint32[...] of
         inclusive [first, last] frame-id runs, block_has_history uint8[nb]) in cox_mesh_msg's layout."""
         nt, nh, ms = C.c_uint64(), C.c_uint64(), C.c_double()
-        self.eng.check(self.eng.fn("meshlayer_history_size")(self.h, obs.h, C.byref(nt), C.byref(nh), C.byref(ms)), "meshlayer_history_size")
+        self._call("meshlayer_history_size", obs.h, C.byref(nt), C.byref(nh), C.byref(ms))
         nt, nh = int(nt.value), int(nh.value)
         out = dict(history_begin=np.zeros(nt + 1, np.uint64), history=np.zeros(nh, np.uint32), block_has_history=np.zeros(self.n_blocks, np.uint8))
-        self.eng.check(self.eng.fn("meshlayer_history")(self.h, obs.h, _fp(out["history_begin"]), _fp(out["history"]), _fp(out["block_has_history"]),
-                                                        C.c_uint64(nt), C.c_uint64(nh), C.c_uint64(self.n_blocks)), "meshlayer_history")
+        self._call("meshlayer_history", obs.h, _fp(out["history_begin"]), _fp(out["history"]), _fp(out["block_has_history"]),
+                   C.c_uint64(nt), C.c_uint64(nh), C.c_uint64(self.n_blocks))
         if with_time:
             out["kernel_ms"] = float(ms.value)
         return out
@@ -1003,20 +948,11 @@ class MeshLayer:
     @staticmethod
     def connected(eng, parts, T_per_part=None, proximity_threshold=1e-4):
         """createConnectedMesh of several meshes, each moved by its T first: dict(xyz, normals, rgb, triangles uint32[nt,3])."""
-        arr = (C.c_void_p * max(1, len(parts)))(*[p.h.value for p in parts])
-        T = None if T_per_part is None else np.ascontiguousarray(np.asarray(T_per_part, np.float32).reshape(len(parts), 7))
-        h, nv, nt = C.c_void_p(), C.c_uint64(), C.c_uint64()
-        eng.check(eng.fn("meshlayer_connected")(arr, _fp(T) if T is not None else None, C.c_uint64(len(parts)), C.c_float(proximity_threshold),
-                                                C.byref(h), C.byref(nv), C.byref(nt)), "meshlayer_connected")
+        mesh = MeshLayer.connected_mesh(eng, parts, T_per_part, proximity_threshold)
         try:
-            nv, nt = int(nv.value), int(nt.value)
-            out = dict(xyz=np.zeros((nv, 3), np.float32), normals=np.zeros((nv, 3), np.float32), rgb=np.zeros((nv, 3), np.uint8),
-                       triangles=np.zeros((nt, 3), np.uint32))
-            eng.check(eng.fn("meshconn_download")(h, *[_fp(out[k]) for k in ("xyz", "normals", "rgb", "triangles")], C.c_uint64(nv), C.c_uint64(nt)),
-                      "meshconn_download")
+            return mesh.download()
         finally:
-            eng.fn("meshconn_destroy", None)(h)
-        return out
+            mesh.close()
 
     @staticmethod
     def connected_mesh(eng, parts, T_per_part=None, proximity_threshold=1e-4):
@@ -1024,13 +960,13 @@ class MeshLayer:
         arr = (C.c_void_p * max(1, len(parts)))(*[p.h.value for p in parts])
         T = None if T_per_part is None else np.ascontiguousarray(np.asarray(T_per_part, np.float32).reshape(len(parts), 7))
         h = C.c_void_p()
-        eng.check(eng.fn("meshlayer_connected")(arr, _fp(T) if T is not None else None, C.c_uint64(len(parts)), C.c_float(proximity_threshold),
-                                                C.byref(h), None, None), "meshlayer_connected")
+        eng.call("meshlayer_connected", arr, _opt(T), C.c_uint64(len(parts)), C.c_float(proximity_threshold), C.byref(h), None, None)
         return ConnectedMesh(eng, h)
 
 
-class ConnectedMesh:
+class ConnectedMesh(_Handle):
     """A connected mesh on the GPU (cox_meshconn_t) and its clean-up in place: DESIGN.md section 7h."""
+    _destroy = "meshconn_destroy"
 
     def __init__(self, eng, h):
         self.eng, self.h = eng, h
@@ -1043,56 +979,44 @@ class ConnectedMesh:
         col = None if rgb is None else np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
         assert (nrm is None or len(nrm) == len(xyz)) and (col is None or len(col) == len(xyz))
         h = C.c_void_p()
-        eng.check(eng.fn("meshconn_from_arrays")(C.c_int(device), _fp(xyz), _fp(nrm) if nrm is not None else None, _fp(col) if col is not None else None,
-                                                 _fp(tri), C.c_uint64(len(xyz)), C.c_uint64(len(tri)), C.byref(h)), "meshconn_from_arrays")
+        eng.call("meshconn_from_arrays", C.c_int(device), _fp(xyz), _opt(nrm), _opt(col), _fp(tri), C.c_uint64(len(xyz)), C.c_uint64(len(tri)),
+                 C.byref(h))
         return cls(eng, h)
-
-    def close(self):
-        if self.h:
-            self.eng.fn("meshconn_destroy", None)(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def size(self):
         """(vertices, triangles)."""
         nv, nt = C.c_uint64(), C.c_uint64()
-        self.eng.check(self.eng.fn("meshconn_size")(self.h, C.byref(nv), C.byref(nt)), "meshconn_size")
+        self._call("meshconn_size", C.byref(nv), C.byref(nt))
         return int(nv.value), int(nt.value)
 
     def clean(self):
         """-> (degenerate triangles, duplicate triangles, unreferenced vertices) removed."""
         r = np.zeros(3, np.uint64)
-        self.eng.check(self.eng.fn("meshconn_clean")(self.h, _fp(r)), "meshconn_clean")
+        self._call("meshconn_clean", _fp(r))
         return tuple(int(v) for v in r)
 
     def smooth_taubin(self, iterations=100, lam=0.5, mu=-0.53):
         """-> HIP-event time of the 2 * iterations half-step launches, in ms."""
         ms = C.c_double()
-        self.eng.check(self.eng.fn("meshconn_smooth_taubin")(self.h, C.c_int(iterations), C.c_float(lam), C.c_float(mu), C.byref(ms)), "meshconn_smooth_taubin")
+        self._call("meshconn_smooth_taubin", C.c_int(iterations), C.c_float(lam), C.c_float(mu), C.byref(ms))
         return float(ms.value)
 
     def simplify_clustering(self, cell_size):
         """-> the new (vertices, triangles)."""
         nv, nt = C.c_uint64(), C.c_uint64()
-        self.eng.check(self.eng.fn("meshconn_simplify_clustering")(self.h, C.c_float(cell_size), C.byref(nv), C.byref(nt)), "meshconn_simplify_clustering")
+        self._call("meshconn_simplify_clustering", C.c_float(cell_size), C.byref(nv), C.byref(nt))
         return int(nv.value), int(nt.value)
 
     def compute_normals(self):
-        self.eng.check(self.eng.fn("meshconn_compute_normals")(self.h), "meshconn_compute_normals")
+        self._call("meshconn_compute_normals")
 
     def download(self):
         """dict(xyz, normals, rgb, triangles uint32[nt,3]), as MeshLayer.connected returns."""
         nv, nt = self.size
         out = dict(xyz=np.zeros((nv, 3), np.float32), normals=np.zeros((nv, 3), np.float32), rgb=np.zeros((nv, 3), np.uint8),
                    triangles=np.zeros((nt, 3), np.uint32))
-        self.eng.check(self.eng.fn("meshconn_download")(self.h, *[_fp(out[k]) for k in ("xyz", "normals", "rgb", "triangles")], C.c_uint64(nv), C.c_uint64(nt)),
-                       "meshconn_download")
+        self._call("meshconn_download", *[_fp(out[k]) for k in ("xyz", "normals", "rgb", "triangles")], C.c_uint64(nv), C.c_uint64(nt))
         return out
 
 
@@ -1123,46 +1047,19 @@ class TrackResult(C.Structure):
 
 
 def track_config(eng, **cfg):
-    c = TrackConfig()
-    eng.fn("track_config_default", None)(C.byref(c))
-    for k, v in cfg.items():
-        if not hasattr(c, k):
-            raise AttributeError(k)
-        setattr(c, k, v)
-    return c
+    return _config(eng, TrackConfig, "track_config_default", cfg)
 
 
-class Tracker:
+class Tracker(_Handle):
     """Scan-to-map registration against a layer (cox_track_t): cfg are fields of cox_track_config."""
+    _destroy = "track_destroy"
+    _borrows = ("layer",)
 
     def __init__(self, eng, layer, **cfg):
         self.eng, self.layer = eng, layer  # (keeps the layer alive)
         self.cfg = track_config(eng, **cfg)
         self.h = C.c_void_p()
-        eng.check(eng.fn("track_create")(layer.h, C.byref(self.cfg), C.byref(self.h)), "track_create")
-
-    def close(self):
-        if self.h:
-            self.eng.fn("track_destroy", None)(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @staticmethod
-    def _ptr(t):
-        if t is None:
-            return None
-        return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-
-    @staticmethod
-    def _pose(T):
-        T = np.ascontiguousarray(T, np.float32)
-        assert T.shape == (7,)
-        return T
+        eng.call("track_create", layer.h, C.byref(self.cfg), C.byref(self.h))
 
     def _result(self, res, T_refined):
         out = res.asdict()
@@ -1179,14 +1076,13 @@ class Tracker:
         vals = torch.empty((n, 7), dtype=torch.float32, device="cuda")
         st = torch.empty(n, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
-        self.eng.check(self.eng.fn("track_evaluate_dev")(self.h, _fp(self._pose(T_G_C)), self._ptr(dx), C.c_uint64(n), self._ptr(vals), self._ptr(st)),
-                       "track_evaluate_dev")
+        self._call("track_evaluate_dev", _fp(_pose(T_G_C)), _ptr(dx), C.c_uint64(n), _ptr(vals), _ptr(st))
         v = vals.cpu().numpy()
         return dict(status=st.cpu().numpy(), pG=v[:, 0:3].copy(), d=v[:, 3].copy(), g=v[:, 4:7].copy())
 
-    def _normal_eq_out(self, call, what):
+    def _normal_eq_out(self, name, *args):
         H, b, cost, counts = np.zeros(36, np.float64), np.zeros(6, np.float64), C.c_double(), (C.c_uint64 * 2)()
-        self.eng.check(call(_fp(H), _fp(b), C.byref(cost), counts), what)
+        self._call(name, *args, _fp(H), _fp(b), C.byref(cost), counts)
         dof = self.cfg.dof
         return dict(H=H.reshape(6, 6)[:dof, :dof].copy(), b=b[:dof].copy(), cost=cost.value, n_used=int(counts[0]), n_considered=int(counts[1]))
 
@@ -1194,24 +1090,11 @@ class Tracker:
         """One evaluation of the normal equations, no update (cox_track_normal_eq_dev): xyz a torch tensor on the layer's GPU, a raw
         device pointer (then n is required) or a host array.  dict(H[dof,dof], b[dof], cost, n_used, n_considered)."""
         xyz, n = self._dev_points(xyz, n)
-        T = self._pose(T_G_C)
-        f = self.eng.fn("track_normal_eq_dev")
-        return self._normal_eq_out(lambda *o: f(self.h, _fp(T), self._ptr(xyz), C.c_uint64(n), *o), "track_normal_eq_dev")
+        return self._normal_eq_out("track_normal_eq_dev", _fp(_pose(T_G_C)), _ptr(xyz), C.c_uint64(n))
 
     def normal_eq_depth_dev(self, T_G_C, depth, w, h, K=None):
         """normal_eq on a depth image on the device (cox_track_normal_eq_depth_dev)."""
-        T, K = self._pose(T_G_C), self._intrinsics(w, h, K)
-        f = self.eng.fn("track_normal_eq_depth_dev")
-        return self._normal_eq_out(lambda *o: f(self.h, _fp(T), self._ptr(depth), C.c_int(w), C.c_int(h), _fp(K), *o), "track_normal_eq_depth_dev")
-
-    @staticmethod
-    def _intrinsics(w, h, K):
-        if K is None:
-            from . import synth
-            K = synth.INTRINSICS[(w, h)]
-        K = np.ascontiguousarray(K, np.float32)
-        assert K.shape == (4,)
-        return K
+        return self._normal_eq_out("track_normal_eq_depth_dev", _fp(_pose(T_G_C)), _ptr(depth), C.c_int(w), C.c_int(h), _fp(_intrinsics(w, h, K)))
 
     def _dev_points(self, xyz, n):
         if isinstance(xyz, np.ndarray):
@@ -1227,7 +1110,7 @@ class Tracker:
         plus T_refined float32[7]."""
         xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
         res, Tr = TrackResult(), np.zeros(7, np.float32)
-        self.eng.check(self.eng.fn("track_refine")(self.h, _fp(self._pose(T_prior)), _fp(xyz), C.c_uint64(len(xyz)), _fp(Tr), C.byref(res)), "track_refine")
+        self._call("track_refine", _fp(_pose(T_prior)), _fp(xyz), C.c_uint64(len(xyz)), _fp(Tr), C.byref(res))
         return self._result(res, Tr)
 
     def refine_dev(self, T_prior, xyz, n=None):
@@ -1236,15 +1119,15 @@ class Tracker:
         if n is None:
             n = xyz.numel() // 3
         res, Tr = TrackResult(), np.zeros(7, np.float32)
-        self.eng.check(self.eng.fn("track_refine_dev")(self.h, _fp(self._pose(T_prior)), self._ptr(xyz), C.c_uint64(n), _fp(Tr), C.byref(res)), "track_refine_dev")
+        self._call("track_refine_dev", _fp(_pose(T_prior)), _ptr(xyz), C.c_uint64(n), _fp(Tr), C.byref(res))
         return self._result(res, Tr)
 
     def refine_depth_dev(self, T_prior, depth, w, h, K=None):
         """cox_track_refine_depth_dev: depth a torch tensor [h,w] on the layer's GPU or a raw device pointer, in the layout of
         Integrator.integrate_depth_dev and Layer.render_dev; K None: synth.INTRINSICS[(w, h)]."""
         res, Tr = TrackResult(), np.zeros(7, np.float32)
-        self.eng.check(self.eng.fn("track_refine_depth_dev")(self.h, _fp(self._pose(T_prior)), self._ptr(depth), C.c_int(w), C.c_int(h),
-                                                             _fp(self._intrinsics(w, h, K)), _fp(Tr), C.byref(res)), "track_refine_depth_dev")
+        self._call("track_refine_depth_dev", _fp(_pose(T_prior)), _ptr(depth), C.c_int(w), C.c_int(h),
+                   _fp(_intrinsics(w, h, K)), _fp(Tr), C.byref(res))
         return self._result(res, Tr)
 
 
@@ -1277,40 +1160,24 @@ class ViewGainStats(C.Structure):
 
 def viewgain_config(eng, **cfg):
     """cox_viewgain_config_default with overrides; K, box_min and box_max take sequences."""
-    c = ViewGainConfig()
-    eng.fn("viewgain_config_default", None)(C.byref(c))
-    for k, v in cfg.items():
-        if not hasattr(c, k):
-            raise AttributeError(k)
-        if k in ("K", "box_min", "box_max"):
-            v = type(getattr(c, k))(*[float(x) for x in v])
-        setattr(c, k, v)
-    return c
+    return _config(eng, ViewGainConfig, "viewgain_config_default", cfg)
 
 
-class ViewGain:
+class ViewGain(_Handle):
     """Scores candidate views against a layer (cox_viewgain_t): cfg are fields of cox_viewgain_config."""
+    _destroy = "viewgain_destroy"
+    _borrows = ("layer",)
 
     def __init__(self, eng, layer, **cfg):
         self.eng, self.layer = eng, layer  # (keeps the layer alive)
         self.cfg = viewgain_config(eng, **cfg)
         self.h = C.c_void_p()
-        eng.check(eng.fn("viewgain_create")(layer.h, C.byref(self.cfg), C.byref(self.h)), "viewgain_create")
-
-    def close(self):
-        if self.h:
-            self.eng.fn("viewgain_destroy", None)(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        eng.call("viewgain_create", layer.h, C.byref(self.cfg), C.byref(self.h))
 
     def view_bytes(self):
         """Workspace bytes one view takes (cox_viewgain_view_bytes)."""
-        return int(self.eng.fn("viewgain_view_bytes", C.c_uint64)(self.h))
+        h = self._guard("viewgain_view_bytes")
+        return int(self.eng.fn("viewgain_view_bytes", C.c_uint64)(h))
 
     def evaluate(self, poses):
         """cox_viewgain_evaluate for host poses [n,7] (qw qx qy qz tx ty tz): dict of numpy arrays over the views -- gain,
@@ -1319,7 +1186,7 @@ class ViewGain:
         n = len(poses)
         rec = np.zeros(n, VIEW_GAIN_DTYPE)
         st = ViewGainStats()
-        self.eng.check(self.eng.fn("viewgain_evaluate")(self.h, _fp(poses), C.c_uint64(n), _fp(rec), C.byref(st)), "viewgain_evaluate")
+        self._call("viewgain_evaluate", _fp(poses), C.c_uint64(n), _fp(rec), C.byref(st))
         out = {k: rec[k].copy() for k in VIEW_GAIN_DTYPE.names}
         out["stats"] = dict(n_samples=int(st.n_samples), n_chunks=int(st.n_chunks), kernel_ms=float(st.kernel_ms))
         return out
@@ -1328,26 +1195,17 @@ class ViewGain:
         """cox_viewgain_evaluate_dev: poses_dev a float32 torch tensor [n,7] on the layer's GPU (or a raw device pointer; then n is
         required), out_dev a tensor of n * 48 bytes (view it with VIEW_GAIN_DTYPE once it is on the host) or a raw pointer; enqueued
         on `stream` (a torch stream, a raw hipStream_t or None = the null stream), not waited for."""
-        def ptr(t):
-            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
         if n is None:
             n = poses_dev.numel() // 7
-        s = getattr(stream, "cuda_stream", stream)
-        self.eng.check(self.eng.fn("viewgain_evaluate_dev")(self.h, ptr(poses_dev), C.c_uint64(n), ptr(out_dev), C.c_void_p(s or 0)), "viewgain_evaluate_dev")
+        self._call("viewgain_evaluate_dev", _ptr(poses_dev), C.c_uint64(n), _ptr(out_dev), _stream(stream))
 
     def visible(self, pose):
         """The visible set of one view (cox_viewgain_visible): dict(voxel_xyz int32[n,3] global voxel indices, cls uint8[n] of
         VG_FREE | VG_OCCUPIED | VG_UNKNOWN | VG_FRONTIER, value float32[n]) in ascending (z, y, x) order."""
-        pose = np.ascontiguousarray(pose, np.float32)
-        assert pose.shape == (7,)
-        f = self.eng.fn("viewgain_visible")
-        n = C.c_uint64()
-        self.eng.check(f(self.h, _fp(pose), C.c_uint64(0), None, None, None, C.byref(n)), "viewgain_visible(query)")
-        k = int(n.value)
-        out = dict(voxel_xyz=np.zeros((k, 3), np.int32), cls=np.zeros(k, np.uint8), value=np.zeros(k, np.float32))
-        if k:
-            self.eng.check(f(self.h, _fp(pose), C.c_uint64(k), _fp(out["voxel_xyz"]), _fp(out["cls"]), _fp(out["value"]), C.byref(n)), "viewgain_visible")
-        return out
+        pose = _pose(pose)
+        out = self._download("viewgain_visible", (((3,), np.int32), ((), np.uint8), ((), np.float32)), lambda a, cap: (_fp(pose), cap, *a),
+                             query="viewgain_visible(query)")
+        return dict(zip(("voxel_xyz", "cls", "value"), out))
 
 
 # ---- collision checks for a planner (include/coxgraph_hip_collide.h) --------------------------------
@@ -1374,65 +1232,38 @@ assert COLLIDE_RECORD_DTYPE.itemsize == 32
 
 def collide_config(eng, **cfg):
     """cox_collide_config_default with overrides; clearing_centre takes a sequence."""
-    c = CollideConfig()
-    eng.fn("collide_config_default", None)(C.byref(c))
-    for k, v in cfg.items():
-        if not hasattr(c, k):
-            raise AttributeError(k)
-        if k == "clearing_centre":
-            v = (C.c_float * 3)(*[float(x) for x in v])
-        setattr(c, k, v)
-    return c
+    return _config(eng, CollideConfig, "collide_config_default", cfg)
 
 
-class CollisionChecker:
+class CollisionChecker(_Handle):
     """Checks planner paths against a layer (cox_collide_t): cfg are fields of cox_collide_config, group_size 32 or 64."""
+    _destroy = "collide_destroy"
+    _borrows = ("layer",)
 
     def __init__(self, eng, layer, group_size=None, **cfg):
         self.eng, self.layer = eng, layer  # (keeps the layer alive)
         self.cfg = collide_config(eng, **cfg)
         self.h = C.c_void_p()
-        eng.check(eng.fn("collide_create")(layer.h, C.byref(self.cfg), C.byref(self.h)), "collide_create")
+        eng.call("collide_create", layer.h, C.byref(self.cfg), C.byref(self.h))
         if group_size is not None:
             self.set_group_size(group_size)
-
-    def close(self):
-        if self.h:
-            self.eng.fn("collide_destroy", None)(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_clearing_centre(self, centre):
         c = np.ascontiguousarray(centre, np.float32)
         assert c.shape == (3,)
-        self.eng.check(self.eng.fn("collide_set_clearing_centre")(self.h, _fp(c)), "collide_set_clearing_centre")
+        self._call("collide_set_clearing_centre", _fp(c))
 
     def set_group_size(self, lanes):
-        self.eng.check(self.eng.fn("collide_set_group_size")(self.h, C.c_int(lanes)), "collide_set_group_size")
+        self._call("collide_set_group_size", C.c_int(lanes))
 
     def set_profiling(self, on=True):
-        self.eng.check(self.eng.fn("collide_set_profiling")(self.h, C.c_int(int(on))), "collide_set_profiling")
+        self._call("collide_set_profiling", C.c_int(int(on)))
 
     def stats(self, reset=False):
         st = CollideStats()
-        self.eng.check(self.eng.fn("collide_stats")(self.h, C.byref(st), C.c_int(int(reset))), "collide_stats")
+        self._call("collide_stats", C.byref(st), C.c_int(int(reset)))
         return dict(n_samples_evaluated=int(st.n_samples_evaluated), n_samples_skipped=int(st.n_samples_skipped), n_launches=int(st.n_launches),
                     kernel_ms=float(st.kernel_ms))
-
-    @staticmethod
-    def _ptr(t):
-        if t is None:
-            return None
-        return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-
-    @staticmethod
-    def _stream(stream):
-        return C.c_void_p(getattr(stream, "cuda_stream", stream) or 0)
 
     @staticmethod
     def _records(rec):
@@ -1443,7 +1274,7 @@ class CollisionChecker:
         xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
         n = len(xyz)
         out = dict(state=np.zeros(n, np.uint8), distance=np.full(n, np.nan, np.float32))
-        self.eng.check(self.eng.fn("collide_points")(self.h, _fp(xyz), C.c_uint64(n), _fp(out["state"]), _fp(out["distance"])), "collide_points")
+        self._call("collide_points", _fp(xyz), C.c_uint64(n), _fp(out["state"]), _fp(out["distance"]))
         return out
 
     def points_dev(self, xyz, state=None, distance=None, n=None, stream=None):
@@ -1451,8 +1282,7 @@ class CollisionChecker:
         `stream` (a torch stream, a raw hipStream_t or None = the null stream), not waited for."""
         if n is None:
             n = xyz.numel() // 3
-        self.eng.check(self.eng.fn("collide_points_dev")(self.h, self._ptr(xyz), C.c_uint64(n), self._ptr(state), self._ptr(distance),
-                                                         self._stream(stream)), "collide_points_dev")
+        self._call("collide_points_dev", _ptr(xyz), C.c_uint64(n), _ptr(state), _ptr(distance), _stream(stream))
 
     def segments(self, a, b):
         """cox_collide_segments for straight segments a[n,3] -> b[n,3]: dict of numpy arrays over the segments -- n_samples,
@@ -1462,15 +1292,14 @@ class CollisionChecker:
         assert a.shape == b.shape
         rec = np.zeros(len(a), COLLIDE_RECORD_DTYPE)
         rec["free_length"] = rec["goal"] = np.nan
-        self.eng.check(self.eng.fn("collide_segments")(self.h, _fp(a), _fp(b), C.c_uint64(len(a)), _fp(rec)), "collide_segments")
+        self._call("collide_segments", _fp(a), _fp(b), C.c_uint64(len(a)), _fp(rec))
         return self._records(rec)
 
     def segments_dev(self, a, b, out, n=None, stream=None):
         """cox_collide_segments_dev: out a tensor of n * 32 bytes (view it with COLLIDE_RECORD_DTYPE on the host) or a raw pointer."""
         if n is None:
             n = a.numel() // 3
-        self.eng.check(self.eng.fn("collide_segments_dev")(self.h, self._ptr(a), self._ptr(b), C.c_uint64(n), self._ptr(out), self._stream(stream)),
-                       "collide_segments_dev")
+        self._call("collide_segments_dev", _ptr(a), _ptr(b), C.c_uint64(n), _ptr(out), _stream(stream))
 
     @staticmethod
     def _csr(offsets, xyz):
@@ -1484,20 +1313,17 @@ class CollisionChecker:
         offsets, xyz = self._csr(offsets, xyz)
         rec = np.zeros(len(offsets) - 1, COLLIDE_RECORD_DTYPE)
         rec["free_length"] = rec["goal"] = np.nan
-        self.eng.check(self.eng.fn("collide_trajectories")(self.h, _fp(offsets), C.c_uint64(len(offsets) - 1), _fp(xyz), C.c_uint64(len(xyz)),
-                                                           _fp(rec)), "collide_trajectories")
+        self._call("collide_trajectories", _fp(offsets), C.c_uint64(len(offsets) - 1), _fp(xyz), C.c_uint64(len(xyz)), _fp(rec))
         return self._records(rec)
 
     def trajectories_dev(self, offsets, n_traj, xyz, n_points, out, stream=None):
-        self.eng.check(self.eng.fn("collide_trajectories_dev")(self.h, self._ptr(offsets), C.c_uint64(n_traj), self._ptr(xyz), C.c_uint64(n_points),
-                                                               self._ptr(out), self._stream(stream)), "collide_trajectories_dev")
+        self._call("collide_trajectories_dev", _ptr(offsets), C.c_uint64(n_traj), _ptr(xyz), C.c_uint64(n_points), _ptr(out), _stream(stream))
 
     def prune_dev(self, parent, feasible, keep, n=None, feasible_stride=1, stream=None):
         """cox_collide_prune_dev: parent int32[n], feasible bytes (bit 0, feasible_stride bytes apart), keep uint8[n] of TREE_*."""
         if n is None:
             n = parent.numel()
-        self.eng.check(self.eng.fn("collide_prune_dev")(self.h, self._ptr(parent), self._ptr(feasible), C.c_uint64(feasible_stride), C.c_uint64(n),
-                                                        self._ptr(keep), self._stream(stream)), "collide_prune_dev")
+        self._call("collide_prune_dev", _ptr(parent), _ptr(feasible), C.c_uint64(feasible_stride), C.c_uint64(n), _ptr(keep), _stream(stream))
 
     def prune(self, parent, feasible):
         """keep uint8[n] of a tree given on the host (staged through torch; the rule runs in cox_collide_prune_dev)."""
@@ -1523,15 +1349,14 @@ class CollisionChecker:
         rec = np.zeros(n, COLLIDE_RECORD_DTYPE)
         rec["free_length"] = rec["goal"] = np.nan
         keep = np.zeros(n, np.uint8)
-        self.eng.check(self.eng.fn("collide_tree")(self.h, _fp(offsets), _fp(parent), C.c_uint64(n), _fp(xyz), C.c_uint64(len(xyz)), _fp(rec),
-                                                   _fp(keep)), "collide_tree")
+        self._call("collide_tree", _fp(offsets), _fp(parent), C.c_uint64(n), _fp(xyz), C.c_uint64(len(xyz)), _fp(rec), _fp(keep))
         out = self._records(rec)
         out["keep"] = keep
         return out
 
     def tree_dev(self, offsets, parent, n_nodes, xyz, n_points, out, keep, stream=None):
-        self.eng.check(self.eng.fn("collide_tree_dev")(self.h, self._ptr(offsets), self._ptr(parent), C.c_uint64(n_nodes), self._ptr(xyz),
-                                                       C.c_uint64(n_points), self._ptr(out), self._ptr(keep), self._stream(stream)), "collide_tree_dev")
+        self._call("collide_tree_dev", _ptr(offsets), _ptr(parent), C.c_uint64(n_nodes), _ptr(xyz), C.c_uint64(n_points), _ptr(out), _ptr(keep),
+                   _stream(stream))
 
 
 class EsdfUpdateStats(C.Structure):
@@ -1550,52 +1375,38 @@ class _BorrowedLayer(Layer):
         self.eng, self.voxel_size, self.h = eng, voxel_size, h
 
     def close(self):
-        self.h = C.c_void_p()
+        self.h = C.c_void_p()  # forgotten first: the owner destroys it, so nothing is left for the base to destroy
+        super().close()
 
 
-class EsdfIntegrator:
+class EsdfIntegrator(_Handle):
     """voxblox EsdfIntegrator::updateFromTsdfLayer (cox_esdf_t): an ESDF bound to a TSDF layer; update() brings it to exactly what
     layer.esdf(**cfg) would return now.  Keywords as Layer.esdf (default_distance_m follows max_distance_m when only that is given)."""
+    _destroy = "esdf_destroy"
+    _borrows = ("tsdf",)
+    layer = None
 
     def __init__(self, eng, layer, max_distance_m=None, min_distance_m=None, default_distance_m=None, min_weight=None):
         self.eng, self.tsdf = eng, layer  # (keeps the TSDF alive)
-        cfg = EsdfConfig()
-        eng.fn("esdf_config_default", None)(C.byref(cfg))
-        for k, v in (("max_distance_m", max_distance_m), ("min_distance_m", min_distance_m), ("default_distance_m", default_distance_m), ("min_weight", min_weight)):
-            if v is not None:
-                setattr(cfg, k, v)
-        if max_distance_m is not None and default_distance_m is None:
-            cfg.default_distance_m = max_distance_m
-        self.cfg = cfg
+        self.cfg = _esdf_config(eng, max_distance_m, min_distance_m, default_distance_m, min_weight)
         self.h = C.c_void_p()
-        self.layer = None
-        eng.check(eng.fn("esdf_create")(layer.h, C.byref(cfg), C.byref(self.h)), "esdf_create")
+        eng.call("esdf_create", layer.h, C.byref(self.cfg), C.byref(self.h))
         lh = C.c_void_p()
-        eng.check(eng.fn("esdf_layer")(self.h, C.byref(lh)), "esdf_layer")
+        self._call("esdf_layer", C.byref(lh))
         self.layer = _BorrowedLayer(eng, layer.voxel_size, lh)
 
     def close(self):
         if self.layer is not None:
             self.layer.close()  # the borrowed layer dies with the handle: later use is refused
-        if self.h:
-            self.eng.fn("esdf_destroy", None)(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
     def update(self):
-        if not self.tsdf.h:  # the TSDF was closed under the integrator: refuse, the C handle would read freed memory
-            raise CoxError(-1, "esdf_update (the TSDF layer is closed)")
         st = EsdfUpdateStats()
-        self.eng.check(self.eng.fn("esdf_update")(self.h, C.byref(st)), "esdf_update")
+        self._call("esdf_update", C.byref(st))
         return st.asdict()
 
     def invalidate(self):
-        self.eng.check(self.eng.fn("esdf_invalidate")(self.h), "esdf_invalidate")
+        self._call("esdf_invalidate")
 
 
 class DepthFuseConfig(C.Structure):
@@ -1616,102 +1427,52 @@ class DepthFuseStats(C.Structure):
 
 def depthfuse_config(eng, **cfg):
     """cox_depthfuse_config_default with fields overridden"""
-    c = DepthFuseConfig()
-    eng.fn("depthfuse_config_default", None)(C.byref(c))
-    for k, v in cfg.items():
-        if not hasattr(c, k):
-            raise AttributeError(k)
-        setattr(c, k, v)
-    return c
+    return _config(eng, DepthFuseConfig, "depthfuse_config_default", cfg)
 
 
-class DepthIntegrator:
+class DepthIntegrator(_Handle):
     """The voxel-projective integrator of a pinhole depth camera (cox_depthfuse_t): cfg are fields of
     cox_depthfuse_config.  Images are [h, w] float32 z-depths (NaN, 0, negative: nothing there) and [h, w, 4] uint8 r, g, b, a;
     K = (fx, fy, cx, cy), None: synth.INTRINSICS[(w, h)]."""
+    _destroy = "depthfuse_destroy"
+    _borrows = ("layer",)
 
     def __init__(self, eng, layer, **cfg):
         self.eng, self.layer = eng, layer  # (keeps the layer alive)
         self.cfg = depthfuse_config(eng, **cfg)
         self.h = C.c_void_p()
-        eng.check(eng.fn("depthfuse_create")(layer.h, C.byref(self.cfg), C.byref(self.h)), "depthfuse_create")
-
-    def close(self):
-        if self.h:
-            self.eng.fn("depthfuse_destroy", None)(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @staticmethod
-    def _pose_K(T_G_C, w, h, K):
-        T = np.ascontiguousarray(T_G_C, np.float32)
-        assert T.shape == (7,)
-        if K is None:
-            from . import synth
-            K = synth.INTRINSICS[(w, h)]
-        K = np.ascontiguousarray(K, np.float32)
-        assert K.shape == (4,)
-        return T, K
-
-    def _live(self, what):
-        if not self.layer.h:  # the layer was closed under the integrator: refuse, the C handle would read freed memory
-            raise CoxError(-1, what + " (the layer is closed)")
+        eng.call("depthfuse_create", layer.h, C.byref(self.cfg), C.byref(self.h))
 
     def integrate(self, T_G_C, depth, rgba=None, K=None):
         """cox_depthfuse_integrate: one frame from host images; the update is enqueued, not waited for (sync())."""
-        self._live("depthfuse_integrate")
-        depth = np.ascontiguousarray(depth, np.float32)
+        depth =np.ascontiguousarray(depth, np.float32)
         assert depth.ndim == 2
         h, w = depth.shape
-        T, K = self._pose_K(T_G_C, w, h, K)
+        T, K = _pose(T_G_C), _intrinsics(w, h, K)
         if rgba is not None:
             rgba = np.ascontiguousarray(rgba, np.uint8)
             assert rgba.shape == (h, w, 4)
-        self.eng.check(self.eng.fn("depthfuse_integrate")(self.h, _fp(T), _fp(depth), None if rgba is None else _fp(rgba), C.c_int(w), C.c_int(h), _fp(K)),
-                       "depthfuse_integrate")
+        self._call("depthfuse_integrate", _fp(T), _fp(depth), _opt(rgba), C.c_int(w), C.c_int(h), _fp(K))
 
     def integrate_dev(self, T_G_C, depth, rgba, w, h, K=None, stream=None):
         """cox_depthfuse_integrate_dev: images are torch tensors on the layer's GPU or raw device pointers (ints), rgba may be
         None; ordered behind `stream` (a torch stream, a raw hipStream_t or None = the null stream), which then waits until the
         frame has read them."""
-        self._live("depthfuse_integrate_dev")
-
-        def ptr(t):
-            if t is None:
-                return None
-            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-        T, K = self._pose_K(T_G_C, w, h, K)
-        s = getattr(stream, "cuda_stream", stream)
-        self.eng.check(self.eng.fn("depthfuse_integrate_dev")(self.h, _fp(T), ptr(depth), ptr(rgba), C.c_int(w), C.c_int(h), _fp(K), C.c_void_p(s or 0)),
-                       "depthfuse_integrate_dev")
+        self._call("depthfuse_integrate_dev", _fp(_pose(T_G_C)), _ptr(depth), _ptr(rgba), C.c_int(w), C.c_int(h), _fp(_intrinsics(w, h, K)),
+                   _stream(stream))
 
     def sync(self):
-        self._live("depthfuse_sync")
-        self.eng.check(self.eng.fn("depthfuse_sync")(self.h), "depthfuse_sync")
+        self._call("depthfuse_sync")
 
     def last_stats(self):
-        self._live("depthfuse_last_stats")
         st = DepthFuseStats()
-        self.eng.check(self.eng.fn("depthfuse_last_stats")(self.h, C.byref(st)), "depthfuse_last_stats")
+        self._call("depthfuse_last_stats", C.byref(st))
         return st.asdict()
 
     def pool_order(self):
         """the layer's block indices int32[n, 3] in pool order"""
-        self._live("depthfuse_pool_order")
-        f = self.eng.fn("depthfuse_pool_order")
-        n = C.c_uint64()
-        st = f(self.h, None, C.c_uint64(0), C.byref(n))
-        if st not in (COX_OK, -7):
-            self.eng.check(st, "depthfuse_pool_order(query)")
-        idx = np.zeros((n.value, 3), np.int32)
-        if n.value:
-            self.eng.check(f(self.h, _fp(idx), C.c_uint64(n.value), C.byref(n)), "depthfuse_pool_order")
-        return idx
+        return self._download("depthfuse_pool_order", (((3,), np.int32),), query="depthfuse_pool_order(query)",
+                              also_ok=(-7,))[0]  # (the query may answer COX_ERR_BUFFER_TOO_SMALL)
 
 
 # ---- dense stereo (include/coxgraph_hip_stereo.h) -------------------------------------------------
@@ -1750,13 +1511,7 @@ DISTORTION_MODELS = {"radtan": 0, "equidistant": 1, "fov": 2, "none": 3}
 
 def stereo_config(eng, **cfg):
     """cox_stereo_config_default with fields overridden"""
-    c = StereoConfig()
-    eng.fn("stereo_config_default", None)(C.byref(c))
-    for k, v in cfg.items():
-        if not hasattr(c, k):
-            raise AttributeError(k)
-        setattr(c, k, v)
-    return c
+    return _config(eng, StereoConfig, "stereo_config_default", cfg)
 
 
 def stereo_calibration(chain):
@@ -1784,15 +1539,17 @@ def rectify_maps(eng, calibration, w, h, scale=1.0):
     n = max(int(w), 0) * max(int(h), 0)
     map0, map1 = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
     K, B, T = np.zeros(4, np.float32), C.c_float(), np.zeros(7, np.float32)
-    eng.check(eng.fn("stereo_rectify_maps")(C.byref(calib), C.c_int(w), C.c_int(h), C.c_double(scale), _fp(map0), _fp(map1), _fp(K), C.byref(B), _fp(T)),
-              "stereo_rectify_maps")
+    eng.call("stereo_rectify_maps", C.byref(calib), C.c_int(w), C.c_int(h), C.c_double(scale), _fp(map0), _fp(map1), _fp(K), C.byref(B), _fp(T))
     return map0.reshape(h, w, 2), map1.reshape(h, w, 2), K, float(B.value), T
 
 
-class StereoMatcher:
+class StereoMatcher(_Handle):
     """Dense stereo of w x h 8-bit pairs (cox_stereo_t); cfg are fields of cox_stereo_config.  Either
     calibration (a camchain, rectified here with `scale`), or maps = (map0, map1) with K_rect and baseline_m, or neither of them
     with K_rect and baseline_m: the pairs are rectified already.  After a calibration, K_rect, baseline_m and T_c0_rect are its."""
+    _destroy = "stereo_destroy"
+    _hattr = "h_"  # (h is the image height)
+    h_ = None
 
     def __init__(self, eng, w, h, calibration=None, maps=None, K_rect=None, baseline_m=None, scale=1.0, device=0, **cfg):
         self.eng, self.w, self.h = eng, int(w), int(h)
@@ -1809,22 +1566,13 @@ class StereoMatcher:
         assert self.K_rect.shape == (4,)
         self.baseline_m = float(baseline_m)
         self.h_ = C.c_void_p()
-        eng.check(eng.fn("stereo_create")(C.c_int(device), C.c_int(w), C.c_int(h), C.byref(self.cfg), None if maps is None else _fp(maps[0]),
-                                          None if maps is None else _fp(maps[1]), _fp(self.K_rect), C.c_float(self.baseline_m), C.byref(self.h_)),
-                  "stereo_create")
+        eng.call("stereo_create", C.c_int(device), C.c_int(w), C.c_int(h), C.byref(self.cfg), None if maps is None else _fp(maps[0]),
+                 None if maps is None else _fp(maps[1]), _fp(self.K_rect), C.c_float(self.baseline_m), C.byref(self.h_))
         self._keep = []  # host arrays of the frames in flight
 
     def close(self):
-        if self.h_:
-            self.eng.fn("stereo_destroy", None)(self.h_)
-            self.h_ = C.c_void_p()
-            self._keep = []
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
+        self._keep = []
 
     def compute_async(self, left, right):
         """cox_stereo_compute without the wait: -> (depth, rgba, disparity), complete after sync()"""
@@ -1833,7 +1581,7 @@ class StereoMatcher:
         depth = np.empty((self.h, self.w), np.float32)
         rgba = np.empty((self.h, self.w, 4), np.uint8)
         disparity = np.empty((self.h, self.w), np.uint16)
-        self.eng.check(self.eng.fn("stereo_compute")(self.h_, _fp(left), _fp(right), _fp(depth), _fp(rgba), _fp(disparity)), "stereo_compute")
+        self._call("stereo_compute", _fp(left), _fp(right), _fp(depth), _fp(rgba), _fp(disparity))
         self._keep.append((left, right, depth, rgba, disparity))
         return depth, rgba, disparity
 
@@ -1848,25 +1596,19 @@ class StereoMatcher:
         """cox_stereo_compute_dev: torch tensors on the matcher's GPU or raw device pointers (ints); ordered behind `stream` (a
         torch stream, a raw hipStream_t or None = the null stream), which then waits until the frame has read left and right.
         The outputs are complete after sync()."""
-        def ptr(t):
-            if t is None:
-                return None
-            return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
-        s = getattr(stream, "cuda_stream", stream)
-        self.eng.check(self.eng.fn("stereo_compute_dev")(self.h_, ptr(left), ptr(right), ptr(depth), ptr(rgba), ptr(disparity), C.c_void_p(s or 0)),
-                       "stereo_compute_dev")
+        self._call("stereo_compute_dev", _ptr(left), _ptr(right), _ptr(depth), _ptr(rgba), _ptr(disparity), _stream(stream))
 
     def stream(self):
         """the matcher's hipStream_t as an int"""
         return int(self.eng.fn("stereo_stream", C.c_void_p)(self.h_) or 0)
 
     def sync(self):
-        self.eng.check(self.eng.fn("stereo_sync")(self.h_), "stereo_sync")
+        self._call("stereo_sync")
         self._keep = []
 
     def last_stats(self):
         st = StereoStats()
-        self.eng.check(self.eng.fn("stereo_last_stats")(self.h_, C.byref(st)), "stereo_last_stats")
+        self._call("stereo_last_stats", C.byref(st))
         return st.asdict()
 
     def download(self, which):
@@ -1876,7 +1618,7 @@ class StereoMatcher:
         shape, dt = {0: ((self.h, self.w), np.uint8), 1: ((self.h, self.w), np.uint8), 2: ((self.h, self.w, int(self.cfg.n_disparities)), np.uint16),
                      3: ((self.h, self.w), np.uint16)}[k]
         out = np.empty(shape, dt)
-        self.eng.check(self.eng.fn("stereo_download")(self.h_, C.c_int(k), _fp(out), C.c_uint64(out.nbytes)), "stereo_download")
+        self._call("stereo_download", C.c_int(k), _fp(out), C.c_uint64(out.nbytes))
         return out
 
 
