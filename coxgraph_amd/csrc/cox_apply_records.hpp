@@ -30,7 +30,7 @@ __device__ __forceinline__ VoxelRef locate_voxel(const LayerView& L, const int4*
   v.gx = b.x + static_cast<int>(lin & 15u);
   v.gy = b.y + static_cast<int>((lin >> 4) & 15u);
   v.gz = b.z + static_cast<int>(lin >> 8);
-  v.ok = pool != kInvalid;
+  v.ok = pool != kInvalid;  // false: a block the binding left without storage -- its records carry valid ids after the merged record walk, callers must skip on !ok
   v.ptr = L.voxels + (static_cast<size_t>(pool) * kVoxelsPerBlock + lin) * kWordsPerVoxel;
   return v;
 }

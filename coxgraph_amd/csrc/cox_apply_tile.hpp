@@ -30,7 +30,7 @@ constexpr u32 kBT = 512, kBW = kBT / 64;  // two waves per SIMD: a tile is a cha
 // the tile id in ONE stable pass whatever the number of touched blocks; up to 255 touched blocks a bucket is a tile, beyond
 // that the tiles b, b + 4096, ... share bucket b and the apply takes them in turn.  (Invalid keys fall into bucket 4095 and
 // are skipped there.)  mask == 0xFFFFFFFF: the key is the tile id itself (piece path), invalid keys have no range.
-__global__ void __launch_bounds__(256) k_block_starts(RecordView V, u32* __restrict__ tile_beg, u32* __restrict__ tile_end, const Counters* cnt, u32 shift, u32 mask) {
+__device__ __forceinline__ void block_starts(const RecordView& V, u32* __restrict__ tile_beg, u32* __restrict__ tile_end, const Counters* cnt, u32 shift, u32 mask) {
   const u32 n = (cnt->err & kErrRecords) ? 0u : *V.d_n;
   const u32* __restrict__ key = V.key[V.info->parity & 1u];
   for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -40,6 +40,17 @@ __global__ void __launch_bounds__(256) k_block_starts(RecordView V, u32* __restr
     if (i == 0 || ((key[i - 1] >> shift) & mask) != t) tile_beg[t] = i;
     if (i + 1 == n || ((key[i + 1] >> shift) & mask) != t) tile_end[t] = i + 1;
   }
+}
+__global__ void __launch_bounds__(256) k_block_starts(RecordView V, u32* __restrict__ tile_beg, u32* __restrict__ tile_end, const Counters* cnt, u32 shift, u32 mask) {
+  block_starts(V, tile_beg, tile_end, cnt, shift, mask);
+}
+// The merged record walk: the binding of the frame's blocks to the layer (cox_walk.hpp) rides at the head of this launch -- its
+// threads are independent of the tile ranges, both are needed by k_apply_block only, and a launch of its own would sit on the
+// ordered chain of every frame (measured: 5.7 us + its gap, 3 % of the frame at 5 cm).  A dropped frame has no ranges but still binds.
+__global__ void __launch_bounds__(256) k_block_starts_bind(RecordView V, u32* __restrict__ tile_beg, u32* __restrict__ tile_end, Counters* cnt, u32 shift, u32 mask,
+                                                           LayerView L, FrameBlocks B, int4* __restrict__ ord_info, u32* layer_err) {
+  bind_touched_blocks(L, B, ord_info, cnt, layer_err);
+  block_starts(V, tile_beg, tile_end, cnt, shift, mask);
 }
 
 // Flush of a batch of `fill` hard records (block-wide; every thread calls it): sort the batch by voxel in LDS (stable
@@ -306,7 +317,8 @@ __global__ void __launch_bounds__(kBT) __attribute__((amdgpu_waves_per_eu(8, 8))
     }
     const int4 info = ord_info[tile / kTPB];
     const u32 pool = static_cast<u32>(info.w);
-    if (pool == kInvalid) continue;  // (uniform; such a block's records carry invalid keys anyway)
+    if (pool == kInvalid) continue;  // (uniform) a block without storage: after the merged record walk its records carry VALID ids (the block
+                                     // keeps its frame ordinal; the binding found no room), so this skip is what keeps the apply off it
     const int gz0 = info.z + static_cast<int>((tile & (kTPB - 1u)) * kSlabs);  // first z slab of the tile
     u32* gblk = L.voxels + (static_cast<size_t>(pool) * kVoxelsPerBlock + (tile & (kTPB - 1u)) * kTV) * kWordsPerVoxel;
     for (u32 i = tid; i < kTV * kWordsPerVoxel; i += kBT) blk[i] = gblk[i];
@@ -528,7 +540,8 @@ __global__ void __launch_bounds__(kWaveTileWaves * 64) k_apply_wave(const FrameP
       tile_end[tile] = 0;
     }
     const u32 pool = static_cast<u32>(info.w);
-    if (pool == kInvalid) continue;  // (uniform; such a block's records carry invalid keys anyway)
+    if (pool == kInvalid) continue;  // (uniform) a block without storage: after the merged record walk its records carry VALID ids (the block
+                                     // keeps its frame ordinal; the binding found no room), so this skip is what keeps the apply off it
     const int gz = info.z + static_cast<int>(tile & (kTilesPerBlock - 1u));
     u32* gblk = L.voxels + (static_cast<size_t>(pool) * kVoxelsPerBlock + (tile & (kTilesPerBlock - 1u)) * kTileVox) * kWordsPerVoxel;
     // ---- T2: voxels (voxel lane + 64 q in registers) and records ----------------------------------------------------------

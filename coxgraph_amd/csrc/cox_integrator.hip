@@ -63,7 +63,8 @@ static_assert(cox_plan::kAxisCapSmall == kAxisCapSmall && cox_plan::kTileShift =
 //   H  bundle hash                            (input only)
 //   P  bundling keys + sort + bundle bounds   (input only)
 //   M  sequential means                       (-> ray arrays, record offsets)
-//   T  touch, emit                            (allocates blocks)
+//   T  touch, emit, binding                   (allocates blocks; merged record walk: touch and emit read the frame's rays and tables
+//                                              only and may run at the tail of M instead -- IntegratorPlan::walk_on_raygen)
 //   R  record partition
 //   U  apply                                  (writes voxels)
 // (simple: H only uploads the parameter block, M is k_rays_simple.)  The stages map to FOUR streams (IntegratorPlan::stage_stream; more
@@ -110,7 +111,9 @@ struct RecordSet {  // lives T .. U
   u32 *pkey[2] = {nullptr, nullptr}, *pstart[2] = {nullptr, nullptr}, *prl[2] = {nullptr, nullptr};
   u64* pbkey = nullptr;                   // piece partition: block key of every piece until k_piece_touch has run
   u32 *plen = nullptr, *pdest = nullptr;  // piece partition: lengths of the sorted pieces, their exclusive scan
-  u32* touched_slots = nullptr;  // [layer ht_cap]
+  u32* touched_slots = nullptr;  // [layer ht_cap] slots of the blocks touched this frame, in ordinal order: of the layer's table, or (merged record walk) of ft_keys
+  u64* ft_keys = nullptr;        // [layer ht_cap] merged record walk: the frame block table (cox_walk.hpp: FrameBlocks); empty between frames
+  u32* ft_ord = nullptr;         // [layer ht_cap]
   int4* ord_info = nullptr;      // [layer ht_cap] (16 * block index, pool index) per block touched this frame
   u32 *blk_beg = nullptr, *blk_end = nullptr;  // [layer ht_cap * 16] record range of every tile (block apply); zero between frames
   u32 *big_of_tile = nullptr, *big_acc = nullptr;  // large tiles (cox_apply_tile.hpp: BigTiles); zero between frames
@@ -401,6 +404,7 @@ static int ensure_capacity(cox_integrator* I, u32 n) {
   // records: the worst case (every ray at maximum length) always fits, so a frame can never overflow
   // unless that bound exceeds the 2^31 record limit of the 32-bit offsets
   I->rcap = static_cast<u32>(std::min<u64>(static_cast<u64>(cap) * steps_max, 0x7FFFFFF0ull));
+  if (I->plan.record_cap) I->rcap = std::min(I->rcap, I->plan.record_cap);  // (tests: a frame with more records is dropped, as beyond 2^31)
   // pieces: every ray at the bound of the longest wave-walked ray (piece_bound); a frame of sequentially walked rays may need
   // more (one piece per step at worst) -- that frame is dropped and reported like a record overflow
   const u32 planes = (steps_max - 1) / 3;
@@ -420,6 +424,11 @@ static int alloc_layer_sized(cox_integrator* I) {
   for (RecordSet& S : I->rs) {
     COX_TRY(dev_realloc(I, &S.touched_slots, slots));
     COX_TRY(dev_realloc(I, &S.ord_info, slots));
+    if (I->method == COX_METHOD_MERGED && !I->plan.walks_pieces()) {  // the frame block table: sized and re-sized with the layer's
+      COX_TRY(dev_realloc(I, &S.ft_keys, slots));
+      COX_TRY(dev_realloc(I, &S.ft_ord, slots));
+      COX_HIP(hipMemset(S.ft_keys, 0xFF, sizeof(u64) * slots));  // empty; every frame's binding leaves it empty again
+    }
     COX_TRY(dev_realloc(I, &S.blk_beg, tiles));
     COX_TRY(dev_realloc(I, &S.blk_end, tiles));
     COX_HIP(hipMemset(S.blk_beg, 0, sizeof(u32) * tiles));
@@ -483,6 +492,7 @@ static inline dim3 grid_for(u32 n, u32 block = 256, u32 cap = 0x7FFFFFFFu) { ret
 // classes whose regions are opened by the submission thread (stages T, R, U and the solve of fast) take their
 // events from a pool of their own
 static inline int event_pool_of(const cox_integrator* I, int cls) {
+  if (cls == COX_KC_TOUCH_EMIT && I->plan.walk_on_raygen) return 0;  // (the walk is enqueued by the caller's thread; the binding carries no events then)
   return (I->submitter && (cls == COX_KC_APPLY || cls == COX_KC_TOUCH_EMIT || cls == COX_KC_RECORD_SORT || cls == COX_KC_FAST_SWEEPS || cls == COX_KC_FAST_ROUND1)) ? 1 : 0;
 }
 static thread_local u64 tl_frame_no = 0;  // the frame whose stages this thread is enqueueing (StageCtx::frame)
@@ -584,6 +594,32 @@ static int stage_point_sort(const StageCtx& c, hipStream_t s) {
   }
   return COX_OK;
 }
+// the merged record walk (RecordTiles, RecordsFullSort): few long rays, so one wave per ray (parallel DDA); the walk found by
+// k_touch_wave is handed to k_emit_wave through the spare sort buffer.  Both read the frame's rays and its own tables only
+// (cox_walk.hpp: FrameBlocks), so the plan may put them on the ray-generation stream (IntegratorPlan::walk_on_raygen).
+static FrameBlocks frame_blocks(const cox_integrator* I, const RecordSet& S) { return FrameBlocks{S.ft_keys, S.ft_ord, S.touched_slots, I->layer->ht_cap - 1}; }
+static void record_walk(const StageCtx& c, hipStream_t s) {
+  cox_integrator* I = c.I;
+  const IntegratorPlan& P = I->plan;
+  FrameSet& F = *c.F;
+  RecordSet& S = *c.S;
+  const u32 fh_mask = I->fh_cap - 1;
+  const FrameBlocks FB = frame_blocks(I, S);
+  if (P.small_axis_cap)
+    hipLaunchKernelGGL(k_touch_wave<kAxisCapSmall>, dim3(P.grid_touch), dim3(256), 0, s, F.d_params, F.rays, FB, S.rec_key[1], I->rcap, F.cnt, F.fh_keys, fh_mask);
+  else
+    hipLaunchKernelGGL(k_touch_wave<kAxisCapLarge>, dim3(2048), dim3(256), 0, s, F.d_params, F.rays, FB, S.rec_key[1], I->rcap, F.cnt, F.fh_keys, fh_mask);
+  hipLaunchKernelGGL(k_emit_wave, dim3(P.grid_touch), dim3(256), 0, s, F.d_params, F.rays, FB, S.rec_key[1], S.rec_key[0], S.rec_ray[0], I->rcap, F.cnt, S.sort_info,
+                     F.fh_keys, fh_mask, P.emit_flags());
+}
+// one thread per block the frame touched (a few hundred at 5 cm, a few thousand at 2 cm); the grid strides.  Where the tile apply
+// follows (RecordTiles), the binding is done at the head of stage U by k_block_starts_bind instead: one launch less on the chain.
+static bool binds_in_apply(const cox_integrator* I) { return I->method == COX_METHOD_MERGED && I->plan.layer_update == LayerUpdate::RecordTiles; }
+static void bind_blocks(const StageCtx& c, hipStream_t s) {
+  cox_integrator* I = c.I;
+  if (binds_in_apply(I)) return;
+  hipLaunchKernelGGL(k_bind_blocks, dim3(16), dim3(256), 0, s, layer_view(I->layer), frame_blocks(I, *c.S), c.S->ord_info, c.F->cnt, I->layer->d_err);
+}
 static int stage_merge(const StageCtx& c, hipStream_t s) {
   cox_integrator* I = c.I;
   FrameSet& F = *c.F;
@@ -621,6 +657,10 @@ static int stage_touch(const StageCtx& c, hipStream_t s) {
   RecordSet& S = *c.S;
   const LayerView L = layer_view(I->layer);
   const u32 fh_mask = I->fh_cap - 1;
+  if (P.walk_on_raygen) {  // the walk ran at the tail of stage M: the binding is all that is left (nothing, where the tile apply binds)
+    bind_blocks(c, s);
+    return COX_OK;
+  }
   TimedRegion t_walk(I, COX_KC_TOUCH_EMIT, s);
   if (P.walks_pieces()) {
     const PieceArrays PA{S.pkey[0], S.pstart[0], S.prl[0], S.pbkey};
@@ -648,15 +688,8 @@ static int stage_touch(const StageCtx& c, hipStream_t s) {
     return COX_OK;
   }
   if (I->method == COX_METHOD_MERGED) {  // (the record offsets are scanned at the end of stage M, off the layer-update chain)
-    // few long rays: one wave per ray (parallel DDA); the walk found by touch is handed to emit through the spare sort buffer
-    if (P.small_axis_cap)
-      hipLaunchKernelGGL(k_touch_wave<kAxisCapSmall>, dim3(P.grid_touch), dim3(256), 0, s, F.d_params, F.rays, L, S.touched_slots, S.rec_key[1], I->rcap, F.cnt,
-                         I->layer->d_err, F.fh_keys, fh_mask);
-    else
-      hipLaunchKernelGGL(k_touch_wave<kAxisCapLarge>, dim3(2048), dim3(256), 0, s, F.d_params, F.rays, L, S.touched_slots, S.rec_key[1], I->rcap, F.cnt,
-                         I->layer->d_err, F.fh_keys, fh_mask);
-    hipLaunchKernelGGL(k_emit_wave, dim3(P.grid_touch), dim3(256), 0, s, F.d_params, F.rays, L, S.rec_key[1], S.rec_key[0], S.rec_ray[0], I->rcap, F.cnt, S.sort_info,
-                       F.fh_keys, fh_mask, S.touched_slots, S.ord_info, P.emit_flags());
+    record_walk(c, s);
+    bind_blocks(c, s);  // (behind emit, which still looks the ordinals up in the table the binding empties)
   } else {
     exclusive_scan_u32(F.rays.nsteps, F.rays.rec_off, &F.cnt->n_ray_slots, I->pcap, I->pcap, &F.cnt->n_records, I->scanws_b, s);
     hipLaunchKernelGGL(k_touch, grid_for(I->pcap, 256, 8192), dim3(256), 0, s, F.d_params, F.rays, L, S.touched_slots, F.cnt, I->layer->d_err, F.fh_keys, fh_mask);
@@ -731,7 +764,11 @@ static int stage_apply(const StageCtx& c, hipStream_t s) {
                          I->layer->d_err, I->layer->h_nblocks);
       break;
     case LayerUpdate::RecordTiles:
-      hipLaunchKernelGGL(k_block_starts, dim3(1024), dim3(256), 0, s, V, S.blk_beg, S.blk_end, F.cnt, P.tile_shift, P.bucket_partition ? 4095u : 0xFFFFFFFFu);
+      if (binds_in_apply(I))
+        hipLaunchKernelGGL(k_block_starts_bind, dim3(1024), dim3(256), 0, s, V, S.blk_beg, S.blk_end, F.cnt, P.tile_shift, P.bucket_partition ? 4095u : 0xFFFFFFFFu, L,
+                           frame_blocks(I, S), S.ord_info, I->layer->d_err);
+      else
+        hipLaunchKernelGGL(k_block_starts, dim3(1024), dim3(256), 0, s, V, S.blk_beg, S.blk_end, F.cnt, P.tile_shift, P.bucket_partition ? 4095u : 0xFFFFFFFFu);
       launch_apply_block(c, s, L, V, I->method == COX_METHOD_MERGED, P.tile_shift, P.bucket_partition);
       break;
     case LayerUpdate::PiecesExpand: {  // (the tile ranges came with the expansion: k_piece_tile_ranges)
@@ -1095,6 +1132,19 @@ static int integrate_device(cox_integrator* I, const float T[7], const float* xy
     COX_HIP(hipStreamWaitEvent(I->producer, I->ev_inputs_read, 0));
   }
   if (in.consumed) COX_HIP(hipEventRecord(in.consumed, s_m));
+  // The record walk, where the plan puts it on the ray-generation stream (behind everything above: the bundle set and the inputs are
+  // not kept waiting for it).  It writes the frame's record set from this thread, so it follows the apply of the frame that used the
+  // set last, t-3.  That frame's stage U has been enqueued -- the submission thread is at most one frame behind (wait_outstanding(1)
+  // above) -- so S.done is recorded and S.used is there to read.  Three record sets: the lanes run at most three frames ahead of
+  // the update.
+  if (I->plan.walk_on_raygen) {
+    if (S.used) COX_HIP(hipStreamWaitEvent(s_m, S.done, 0));
+    {
+      TimedRegion t_walk(I, COX_KC_TOUCH_EMIT, s_m);
+      record_walk(ctx, s_m);
+    }
+    if (stage_stream(I, 3, slot) != s_m) COX_HIP(hipEventRecord(F.hand[2], s_m));  // stage T waits for the walk, not only for the merge
+  }
   COX_HIP(hipGetLastError());
   // T, R, U (layer update): on the submission thread when there is one
   auto stage_b = [ctx, chain, foreign_writer]() -> int {

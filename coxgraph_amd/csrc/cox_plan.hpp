@@ -19,7 +19,8 @@ namespace cox_plan {
 #define COX_PLAN_SWITCHES(X)                                                                                                                   \
   X(APPLY) X(APPLY_WAVE) X(BIG_CHUNK) X(BUCKETS) X(COPY_THREADS) X(DEBUG) X(DEPTH_CONVERT) X(FAST_CAP) X(FAST_FENCE) X(FAST_GROUPS)             \
   X(FAST_ROUNDS) X(FAST_SEQUENTIAL) X(FAST_STREAMS) X(GRAPH) X(GRID_APPLY) X(GRID_APPLY_WAVE) X(GRID_MERGE) X(GRID_TOUCH) X(H2D) X(H2D_GROUPS) \
-  X(INPUT_STREAM) X(NO_GRAPH) X(PARTITION) X(QUEUES) X(SPLIT_TILES) X(STREAMS) X(STREAM_MAP) X(SUBMIT_THREAD) X(TILE) X(TIMELINE) X(WAVE_TILE_MAX)
+  X(INPUT_STREAM) X(NO_GRAPH) X(PARTITION) X(QUEUES) X(RECORD_CAP) X(SPLIT_TILES) X(STREAMS) X(STREAM_MAP) X(SUBMIT_THREAD) X(TILE) X(TIMELINE) X(WALK)       \
+  X(WAVE_TILE_MAX)
 #define COX_PLAN_ENUM(n) k##n,
 #define COX_PLAN_NAME(n) "COX_" #n,
 enum Switch { COX_PLAN_SWITCHES(COX_PLAN_ENUM) kNumSwitches };
@@ -65,11 +66,14 @@ struct IntegratorPlan {
   uint32_t grid_apply = 8192, grid_apply_wave = 2048, grid_merge = 4096, grid_touch = 2048;  // grid-stride kernels: any size is correct
   uint32_t steps_max = 0;       // upper bound of a ray's step count (ray_length_in_steps + 1) for this configuration
   bool small_axis_cap = false;  // no ray can cross more than kAxisCapSmall - 2 planes of one axis
+  uint32_t record_cap = 0;      // records a frame may have at most (tests: COX_RECORD_CAP); 0 = the worst case of the point capacity, which no frame exceeds
   // ---- streams, in creation order: the input stream, the alternate ray-generation stream, the stage streams back to back
   int stage_stream[kNumStages] = {0, 0, 0, 1, 1, 2};  // stage -> stage stream; equal streams are adjacent
   bool alt_raygen_stream = false;  // stages H, P, M of the odd frame slots run on a stream of their own
   bool input_stream = true;        // host inputs are staged on a stream of their own
   int n_streams = 0;               // distinct streams in all
+  bool walk_on_raygen = false;     // merged record walk (k_touch_wave, k_emit_wave) at the tail of stage M, on the frame's ray-generation stream;
+                                   // stage T is then the binding of the frame's blocks to the layer alone
   // ---- host side
   bool use_graphs = false;     // stages replayed as captured HIP graphs
   bool submit_thread = true;   // stages T, R, U enqueued by a thread of the integrator's own
@@ -132,6 +136,9 @@ IntegratorPlan resolve_plan(int method, const cox_tsdf_config& cfg, float voxel_
     // per-record work, not by the round trips per tile.
     if (v[kTILE]) p.tile_shift = num(kTILE) == 9 ? 9u : 8u;
   }
+  // COX_RECORD_CAP=<n> (tests): record buffers of n records instead of the worst case, so that a frame can overflow them and be
+  // dropped as a whole (kErrRecords) without a cloud of millions of points.  Record walks of simple and merged only.
+  if (v[kRECORD_CAP] && !fast && !p.walks_pieces() && num(kRECORD_CAP) > 0) p.record_cap = static_cast<uint32_t>(num(kRECORD_CAP));
   if (v[kAPPLY_WAVE]) p.wave_apply = num(kAPPLY_WAVE) != 0;
   if (v[kSPLIT_TILES]) p.split_big_tiles = num(kSPLIT_TILES) != 0;
   if (v[kBIG_CHUNK]) p.big_chunk = static_cast<uint32_t>(std::max<int>(kBigChunkMin, num(kBIG_CHUNK)));
@@ -224,6 +231,19 @@ IntegratorPlan resolve_plan(int method, const cox_tsdf_config& cfg, float voxel_
   }
   std::copy(map, map + kNumStages, p.stage_stream);
   p.n_streams = p.n_stage_streams() + (p.alt_raygen_stream ? 1 : 0) + (p.input_stream ? 1 : 0);
+
+  // ---- where the merged record walk runs.  Block ordinals come from a table of the frame's own (cox_walk.hpp), so the walk and emit
+  // depend on the frame's rays alone and may run on the ray-generation stream; only the binding has to stay in the layer's frame
+  // order.  Where T, R and U share one stream and two ray-generation lanes serve every other frame each (four queues, 10 and 5 cm),
+  // that stream is the longest chain of a frame and the lanes stand half idle: the walk goes to the lanes.  With a stream each for
+  // T R and U the lanes would become the longest chain, so the walk stays in stage T there.
+  // COX_WALK=raygen|update replaces the rule.  Stage graphs keep the walk in stage T (a stage is captured once, and the wait for the
+  // record set's previous user belongs in front of the walk).
+  {
+    const bool can = merged && !p.walks_pieces() && !p.use_graphs;
+    const bool rule = p.alt_raygen_stream && p.stage_stream[3] == p.stage_stream[5];
+    p.walk_on_raygen = can && (is(kWALK, "raygen") ? true : is(kWALK, "update") ? false : rule);
+  }
 
   // ---- fast.  At 5 cm two rounds settle every frame of the benchmark stream; at 2 cm and 1 cm nine frames in ten have a ray that
   // outgrows its round-1 list, and a frame that ends so is redone by ONE lane (14 and 4 frames/s): eight rounds there, and longer lists

@@ -1,6 +1,7 @@
 // The record walk (stage T): touch (allocate blocks, give every block touched this frame a dense ordinal) and emit ((voxel id, ray)
 // records, ray-major), lane per ray and wave per ray (parallel DDA) -- part of cox_integrator.hip (included there, in this order:
-// the kernels use what is defined above them in that file).
+// the kernels use what is defined above them in that file).  The wave walk of `merged` takes its ordinals from a table of the
+// frame's own and leaves the layer to k_bind_blocks (FrameBlocks, below), so it may run ahead of the layer update.
 #pragma once
 
 // ---- touch: allocate blocks, give every block touched this frame a dense ordinal ---------------
@@ -285,9 +286,78 @@ __device__ __forceinline__ u32 touch_block(const FrameParams& P, const LayerView
   return slot;
 }
 
+// ---- the frame block table (merged record walk) ---------------------------------------------------------------------------------
+// The ordinal of a block is a dense number per distinct block key of THIS frame, so the walk takes it from a table of the frame's
+// own (one per record set: open addressing on the packed block key, sized with the layer's table, so a frame that fits the layer's
+// fits the frame's) and touches no layer word.  The layer comes in with the binding (k_bind_blocks), one thread per touched block:
+// the only step of a frame that has to follow the previous frame's update.
+struct FrameBlocks {
+  u64* keys;   // [mask + 1] block key per slot; empty between frames (the binding empties the slots it reads)
+  u32* ord;    // [mask + 1] ordinal of the slot's key (valid while the key is there)
+  u32* slots;  // [mask + 1] the occupied slots in ordinal order: slots[0, n_touched)
+  u32 mask;
+};
+// the first inserter of a key hands out its ordinal (the walk; emit runs in a later launch and only looks up)
+__device__ __forceinline__ void touch_frame_block(const FrameBlocks& B, u64 bkey, Counters* cnt) {
+  bool fresh;
+  const u32 slot = ht_insert(B.keys, B.mask, bkey, &fresh);
+  if (slot == kInvalid) {  // more distinct blocks than the layer's table has slots: the layer could not take them either
+    atomicOr(&cnt->err, kErrTable);
+    return;
+  }
+  if (fresh) {
+    const u32 ord = atomicAdd(&cnt->n_touched, 1u);
+    B.ord[slot] = ord;
+    B.slots[ord] = slot;
+  }
+}
+__device__ __forceinline__ u32 frame_block_ord(const FrameBlocks& B, u64 bkey) {
+  const u32 slot = ht_find(B.keys, B.mask, bkey);
+  return slot != kInvalid ? B.ord[slot] : kInvalid;
+}
+// Binding: block ordinal -> layer.  Inserts the key into the layer's table, gives a new block its storage exactly as touch_block
+// does, publishes what the update kernels need of the block (ord_info) and empties the frame table's slot.  Every key is bound by
+// one thread (the frame table holds it once), so the (slot, pool) pair of a fresh key has one writer; keys of earlier frames
+// were bound by earlier launches.
+__device__ __forceinline__ void bind_touched_blocks(const LayerView& L, const FrameBlocks& B, int4* __restrict__ ord_info, Counters* cnt, u32* layer_err) {
+  const u32 n_touched = cnt->n_touched;
+  for (u32 ord = blockIdx.x * blockDim.x + threadIdx.x; ord < n_touched; ord += gridDim.x * blockDim.x) {
+    const u32 fslot = B.slots[ord];
+    const u64 bkey = B.keys[fslot];
+    B.keys[fslot] = kEmptyKey;
+    u32 pool = kInvalid;
+    bool fresh;
+    const u32 slot = ht_insert(L.ht_keys, L.ht_mask, bkey, &fresh);
+    if (slot == kInvalid) {
+      atomicOr(layer_err, kErrTable);
+    } else if (fresh) {
+      pool = atomicAdd(L.d_nblocks, 1u);
+      if (pool < L.capacity) {
+        L.ht_vals[slot] = pool;
+        L.block_keys[pool] = bkey;
+        atomicAdd(&cnt->n_new_blocks, 1u);
+      } else {
+        atomicSub(L.d_nblocks, 1u);     // the counter settles at the capacity
+        atomicOr(layer_err, kErrPool);  // ht_vals[slot] stays kInvalid: every later frame that meets the key reports the error again
+        pool = kInvalid;
+      }
+    } else {
+      pool = L.ht_vals[slot];
+    }
+    if (pool == kInvalid) atomicOr(&cnt->err, kErrPool);  // block without storage: its updates are lost (the apply kernels skip it)
+    int bx, by, bz;
+    unpack_key(bkey, &bx, &by, &bz);
+    ord_info[ord] = make_int4(bx * 16, by * 16, bz * 16, static_cast<int>(pool));
+  }
+}
+// a launch of its own where no k_block_starts follows (full record sort); the tile apply binds at the head of k_block_starts_bind
+__global__ void __launch_bounds__(256) k_bind_blocks(LayerView L, FrameBlocks B, int4* __restrict__ ord_info, Counters* cnt, u32* layer_err) {
+  bind_touched_blocks(L, B, ord_info, cnt, layer_err);
+}
+
 template <u32 kAxisCap>
-__global__ void __launch_bounds__(256) k_touch_wave(const FrameParams* __restrict__ Pp, RayArrays R, LayerView L, u32* __restrict__ touched_slots, u32* __restrict__ path_out,
-                                                    u32 rec_cap, Counters* cnt, u32* layer_err, const u64* __restrict__ fh_keys, u32 fh_mask) {
+__global__ void __launch_bounds__(256) k_touch_wave(const FrameParams* __restrict__ Pp, RayArrays R, FrameBlocks B, u32* __restrict__ path_out, u32 rec_cap, Counters* cnt,
+                                                    const u64* __restrict__ fh_keys, u32 fh_mask) {
   const FrameParams P = *Pp;
   __shared__ float lds_t[4][3 * kAxisCap];
   __shared__ u32 lds_path[4][3 * kAxisCap];
@@ -333,7 +403,7 @@ __global__ void __launch_bounds__(256) k_touch_wave(const FrameParams* __restric
         const int src = kept_below ? (63 - __clzll(static_cast<long long>(kept_below))) : 0;
         const u64 prev_kept = __shfl(bkey, src, 64);
         const u64 prev = kept_below ? prev_kept : carry;
-        if (act && !skip && bkey != prev) touch_block(P, L, bkey, touched_slots, cnt, layer_err);
+        if (act && !skip && bkey != prev) touch_frame_block(B, bkey, cnt);
         if (kept) carry = __shfl(bkey, 63 - __clzll(static_cast<long long>(kept)), 64);
       }
       wave_lds_handover();  // the next ray of this wave reuses the LDS scratch
@@ -347,19 +417,17 @@ __global__ void __launch_bounds__(256) k_touch_wave(const FrameParams* __restric
         const u64 bkey = pack_key(x >> 4, y >> 4, z >> 4);
         if (bkey == last_bkey) continue;
         last_bkey = bkey;
-        touch_block(P, L, bkey, touched_slots, cnt, layer_err);
+        touch_frame_block(B, bkey, cnt);
       }
     }
   }
 }
 
-__global__ void __launch_bounds__(256) k_emit_wave(const FrameParams* __restrict__ Pp, RayArrays R, LayerView L, const u32* __restrict__ path_in, u32* __restrict__ rec_key,
+__global__ void __launch_bounds__(256) k_emit_wave(const FrameParams* __restrict__ Pp, RayArrays R, FrameBlocks B, const u32* __restrict__ path_in, u32* __restrict__ rec_key,
                                                    u32* __restrict__ rec_ray, u32 rec_cap, Counters* cnt, SortInfo* sort_info,
-                                                   const u64* __restrict__ fh_keys, u32 fh_mask, const u32* __restrict__ touched_slots, int4* __restrict__ ord_info,
-                                                   int by_block) {
+                                                   const u64* __restrict__ fh_keys, u32 fh_mask, int by_block) {
   const FrameParams P = *Pp;
   const u32 n_slots = uniform_u32(cnt->n_ray_slots);
-  fill_ord_info(L, touched_slots, ord_info, cnt->n_touched);
   const bool overflow = uniform_u32(cnt->n_records) > rec_cap;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     // ordinals are < n_touched; kInvalid's low bits (all ones) must sort after every valid id
@@ -407,9 +475,7 @@ __global__ void __launch_bounds__(256) k_emit_wave(const FrameParams* __restrict
         const bool is_head = act && bkey != prev;
         u32 ord = kInvalid;
         if (is_head) {
-          const u32 slot = ht_find(L.ht_keys, L.ht_mask, bkey);
-          ord = (slot != kInvalid && L.ht_vals[slot] != kInvalid) ? L.ht_ord[slot] : kInvalid;
-          if (ord == kInvalid) atomicOr(&cnt->err, kErrPool);  // block without storage: this update is lost
+          ord = frame_block_ord(B, bkey);  // (a block the binding leaves without storage keeps its ordinal: the apply kernels skip it)
         }
         // every lane takes the ordinal of the nearest head at or below it, or the carry of the previous round
         const u64 heads = __ballot(is_head);
@@ -435,9 +501,7 @@ __global__ void __launch_bounds__(256) k_emit_wave(const FrameParams* __restrict
           const u64 bkey = pack_key(x >> 4, y >> 4, z >> 4);
           if (bkey != last_bkey) {
             last_bkey = bkey;
-            const u32 slot = ht_find(L.ht_keys, L.ht_mask, bkey);
-            last_ord = (slot != kInvalid && L.ht_vals[slot] != kInvalid) ? L.ht_ord[slot] : kInvalid;
-            if (last_ord == kInvalid) atomicOr(&cnt->err, kErrPool);  // block without storage: this update is lost
+            last_ord = frame_block_ord(B, bkey);
           }
           if (last_ord != kInvalid) vid = (last_ord << 12) | static_cast<u32>((x & 15) | ((y & 15) << 4) | ((z & 15) << 8));
         }

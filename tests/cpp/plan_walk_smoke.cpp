@@ -1,0 +1,96 @@
+// Where the merged record walk runs (IntegratorPlan::walk_on_raygen, COX_WALK) without a GPU: every (method, voxel size, queue budget).
+// The expectation is written down here from the rule -- the walk goes to the ray-generation lanes where stages T, R and U share one
+// stream and the alternate ray-generation stream exists, which with the default maps is `merged` at 10 and 5 cm on a budget of four
+// queues -- not taken from resolve_plan's output.  COX_WALK wins over the rule wherever there is a record walk to place, and the
+// switch changes no other field of the plan.  Exit code 0 = all good.
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <string>
+
+#include "../../coxgraph_amd/csrc/cox_plan.hpp"
+
+using namespace cox_plan;
+typedef std::map<std::string, std::string> Env;
+
+static int g_failures = 0;
+static const int kNotGiven = -1;
+
+static cox_tsdf_config config_of(double voxel) {
+  cox_tsdf_config cfg;
+  std::memset(&cfg, 0, sizeof(cfg));
+  const bool v10 = voxel > 0.07, v5 = !v10 && voxel > 0.03, v2 = !v10 && !v5 && voxel > 0.015;
+  cfg.default_truncation_distance = v10 ? 0.30f : v5 ? 0.15f : v2 ? 0.06f : 0.03f;
+  cfg.max_ray_length_m = v10 ? 10.0f : v5 ? 6.0f : 3.0f;
+  return cfg;
+}
+static IntegratorPlan resolve(int method, double voxel, const Env& env, int budget) {
+  const cox_tsdf_config cfg = config_of(voxel);
+  auto lookup = [&](const char* name) -> const char* {
+    const auto it = env.find(name);
+    return it == env.end() ? nullptr : it->second.c_str();
+  };
+  if (budget == kNotGiven) return resolve_plan(method, cfg, static_cast<float>(voxel), lookup);
+  return resolve_plan(method, cfg, static_cast<float>(voxel), lookup, budget);
+}
+static Env with(Env env, const char* name, const char* value) {
+  env[name] = value;
+  return env;
+}
+static std::string tag(int method, double voxel, int budget, const Env& env) {
+  std::string s = std::string(method == COX_METHOD_SIMPLE ? "simple" : method == COX_METHOD_MERGED ? "merged" : "fast") + " @" + std::to_string(voxel) +
+                  " budget " + (budget == kNotGiven ? std::string("-") : std::to_string(budget));
+  for (const auto& kv : env) s += " " + kv.first + "=" + kv.second;
+  return s;
+}
+static void expect(const std::string& what, bool got, bool want) {
+  if (got != want) {
+    std::printf("FAIL %s: walk_on_raygen %d, expected %d\n", what.c_str(), got ? 1 : 0, want ? 1 : 0);
+    ++g_failures;
+  }
+}
+#define FIELD(f) \
+  if (!(a.f == b.f)) { std::printf("FAIL %s: " #f " changes with COX_WALK\n", what.c_str()); ++g_failures; }
+static void same_but_walk(const std::string& what, const IntegratorPlan& a, const IntegratorPlan& b) {
+  FIELD(layer_update) FIELD(bucket_partition) FIELD(tile_shift) FIELD(wave_apply) FIELD(split_big_tiles) FIELD(big_chunk) FIELD(wave_tile_max)
+  FIELD(grid_apply) FIELD(grid_apply_wave) FIELD(grid_merge) FIELD(grid_touch) FIELD(steps_max) FIELD(small_axis_cap)
+  for (int k = 0; k < 6; ++k) FIELD(stage_stream[k])
+  FIELD(alt_raygen_stream) FIELD(input_stream) FIELD(n_streams) FIELD(use_graphs) FIELD(submit_thread) FIELD(copy_threads) FIELD(h2d_kernel)
+  FIELD(h2d_groups) FIELD(depth_convert_on_input_stream) FIELD(timeline) FIELD(debug)
+  FIELD(fast.streams) FIELD(fast.rounds) FIELD(fast.cap0) FIELD(fast.cap1) FIELD(fast.relax_groups) FIELD(fast.fences) FIELD(fast.force_sequential)
+}
+
+static const int kMethods[3] = {COX_METHOD_SIMPLE, COX_METHOD_MERGED, COX_METHOD_FAST};
+static const double kVoxels[4] = {0.10, 0.05, 0.02, 0.01};
+static const int kBudgets[8] = {1, 2, 3, 4, 5, 8, 16, kNotGiven};
+
+int main() {
+  for (int method : kMethods)
+    for (double vx : kVoxels)
+      for (int b : kBudgets) {
+        const bool merged = method == COX_METHOD_MERGED, coarse = vx > 0.03;
+        // the rule: merged walks records at 10 and 5 cm (pieces below); four queues leave H P M x2 | T R U
+        expect(tag(method, vx, b, {}), resolve(method, vx, {}, b).walk_on_raygen, merged && coarse && b == 4);
+        // the environments in which the switch is tried: the record walk exists for merged at every voxel size once records are asked for
+        const Env envs[] = {{}, {{"COX_PARTITION", "records"}}, {{"COX_APPLY", "records"}}, {{"COX_PARTITION", "records"}, {"COX_BUCKETS", "0"}},
+                            {{"COX_SUBMIT_THREAD", "0"}}, {{"COX_STREAMS", "3p"}}, {{"COX_STREAMS", "2"}}, {{"COX_GRAPH", "1"}}};
+        for (const Env& env : envs) {
+          const IntegratorPlan base = resolve(method, vx, env, b);
+          const IntegratorPlan on = resolve(method, vx, with(env, "COX_WALK", "raygen"), b), off = resolve(method, vx, with(env, "COX_WALK", "update"), b);
+          const bool records = merged && (coarse || env.count("COX_PARTITION") || env.count("COX_APPLY"));
+          const bool graphs = env.count("COX_GRAPH") != 0;  // stage graphs keep the walk in stage T
+          expect(tag(method, vx, b, with(env, "COX_WALK", "raygen")), on.walk_on_raygen, records && !graphs);
+          expect(tag(method, vx, b, with(env, "COX_WALK", "update")), off.walk_on_raygen, false);
+          same_but_walk(tag(method, vx, b, with(env, "COX_WALK", "raygen")), on, base);
+          same_but_walk(tag(method, vx, b, with(env, "COX_WALK", "update")), off, base);
+          // anything else is no choice: the rule holds
+          expect(tag(method, vx, b, with(env, "COX_WALK", "lanes")), resolve(method, vx, with(env, "COX_WALK", "lanes"), b).walk_on_raygen, base.walk_on_raygen);
+        }
+        // the rule follows the streams, not the budget's number: H P M x2 | T R U chosen by hand has the walk on the lanes at any budget
+        expect(tag(method, vx, b, {{"COX_STREAMS", "3p"}, {"COX_PARTITION", "records"}}),
+               resolve(method, vx, {{"COX_STREAMS", "3p"}, {"COX_PARTITION", "records"}}, b).walk_on_raygen, merged);
+        expect(tag(method, vx, b, {{"COX_STREAMS", "2"}}), resolve(method, vx, {{"COX_STREAMS", "2"}}, b).walk_on_raygen, false);
+      }
+  std::printf("%s (%d failures)\n", g_failures ? "FAILED" : "ok", g_failures);
+  return g_failures ? 1 : 0;
+}
