@@ -877,12 +877,15 @@ __global__ void __launch_bounds__(256) k_resample_blocks(LayerConstView A, Rigid
 static int merge_device_blocks(cox_layer* L, const int32_t* d_idx, const u32* d_src, const u32* d_src_index, u32 n) {
   if (n == 0) return COX_OK;
   {
+    // the contract of the uploads (upload_from_device): room for nb + n blocks is made before the first key goes in, and a
+    // layer that may not or cannot grow is left untouched
     u32 nb0, err0;
     int st0 = layer_read_counters(L, &nb0, &err0);
     if (st0 != COX_OK) return st0;
-    if (static_cast<u64>(nb0) + n > L->capacity && L->auto_grow) {
+    if (static_cast<u64>(nb0) + n > L->capacity) {
+      if (!L->auto_grow) return COX_ERR_POOL_EXHAUSTED;
       st0 = cox_internal_layer_reserve(L, std::max<u64>(2 * L->capacity, static_cast<u64>(nb0) + n));
-      if (st0 != COX_OK && st0 != COX_ERR_OUT_OF_MEMORY) return st0;
+      if (st0 != COX_OK) return st0 == COX_ERR_OUT_OF_MEMORY ? COX_ERR_POOL_EXHAUSTED : st0;
     }
   }
   u32* d_pool = nullptr;

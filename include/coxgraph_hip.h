@@ -132,7 +132,9 @@ int cox_layer_upload(cox_layer_t* layer, const int32_t* block_idx_xyz, const uin
  * doubled automatically (integrators: once it is half full, before the next frame is enqueued; uploads / merges: before
  * they insert) until hipMalloc refuses; cox_layer_reserve does it explicitly.  Contents are preserved, nothing may be in
  * flight on the layer from OTHER threads.  cox_layer_set_auto_grow(layer, 0) pins the capacity: a frame that runs out then
- * reports COX_ERR_POOL_EXHAUSTED at sync, and so does every later frame that meets a block left without storage. */
+ * reports COX_ERR_POOL_EXHAUSTED at sync, and so does every later frame that meets a block left without storage.  An upload
+ * or a merge that may need more blocks than fit (blocks held + blocks brought) returns COX_ERR_POOL_EXHAUSTED before it
+ * inserts anything: the layer is unchanged and no error stays behind. */
 int cox_layer_reserve(cox_layer_t* layer, uint64_t capacity_blocks);
 int cox_layer_capacity(cox_layer_t* layer, uint64_t* capacity_blocks);
 int cox_layer_set_auto_grow(cox_layer_t* layer, int on);

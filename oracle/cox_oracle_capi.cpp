@@ -144,7 +144,7 @@ int coxo_layer_upload(coxo_layer* l, const int32_t* idx, const uint32_t* vox, ui
 
 // mergeLayerAintoLayerB(A, [T_B_A,] B): T == nullptr merges on the same grid
 int coxo_layer_merge(const coxo_layer* a, const float T[7], coxo_layer* b) {
-  if (!a || !b) return COX_ERR_INVALID_ARG;
+  if (!a || !b || a == b) return COX_ERR_INVALID_ARG;  // the HIP engine's contract: a layer is not merged into itself
   if (!T) {
     if (a->layer.voxel_size != b->layer.voxel_size || a->layer.vps != b->layer.vps) return COX_ERR_INVALID_ARG;
     mergeLayerAintoLayerB(a->layer, &b->layer);

@@ -6,8 +6,9 @@ vector within 1e-4 abs, Jacobians within 1e-3 rel, reduced H / b / cost within 1
 import numpy as np
 import pytest
 
+import layer_ref
 from coxgraph_amd import synth
-from coxgraph_amd.capi import Layer, RegPoints, Registration, words_to_fields
+from coxgraph_amd.capi import Layer, RegPoints, Registration
 from util import run_frames
 
 pytestmark = pytest.mark.gpu
@@ -17,17 +18,7 @@ def registration_points(layer, trunc, min_weight=1.0):
     """voxgraph 'implicit_to_implicit' point set: voxel centres with weight > min_weight and |d| < trunc,
     in (z,y,x) block order / linear voxel order -> float32 [n,5] = x,y,z,distance,weight (submap frame)."""
     idx, vox = layer.download()
-    d, w, _ = words_to_fields(vox)
-    vs = np.float32(layer.voxel_size)
-    lin = np.arange(4096)
-    loc = np.stack([lin % 16, (lin // 16) % 16, lin // 256], axis=1)
-    out = []
-    for b in range(len(idx)):
-        m = (w[b] > min_weight) & (np.abs(d[b]) < trunc)
-        g = idx[b][None, :] * 16 + loc[m]
-        c = ((g.astype(np.float32) + 0.5) * vs).astype(np.float32)
-        out.append(np.concatenate([c, d[b][m, None], w[b][m, None]], axis=1))
-    return np.concatenate(out, axis=0).astype(np.float32)
+    return layer_ref.relevant_points_ref(idx, vox, layer.voxel_size, min_weight, trunc)
 
 
 @pytest.fixture(scope="module")
