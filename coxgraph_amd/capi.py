@@ -647,7 +647,8 @@ class Registration(_Handle):
         pd = np.ascontiguousarray(pose_read, np.float64)
         assert pr.shape == (4,) and pd.shape == (4,)
         if sample_idx is None:
-            return pr, pd, None, (getattr(self, "stored_n", None) or self.ref.n)
+            stored = getattr(self, "stored_n", None)  # (0 is a stored set too: an empty one)
+            return pr, pd, None, (self.ref.n if stored is None else stored)
         si = np.ascontiguousarray(sample_idx, np.uint32)
         return pr, pd, si, si.shape[0]
 

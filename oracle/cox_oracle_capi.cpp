@@ -330,9 +330,10 @@ static int regRun(coxo_reg* reg, const double pose_ref[4], const double pose_rea
   const size_t npts = reg->ref->pts.size();
   if (!sample_idx && reg->has_stored) {  // cox_reg_set_samples
     if (n_res != reg->stored.size()) return COX_ERR_INVALID_ARG;
-    sample_idx = reg->stored.data();
+    sample_idx = reg->stored.data();  // (may be null for an empty stored set: n_res is 0 then)
+  } else if (!sample_idx && n_res != npts) {
+    return COX_ERR_INVALID_ARG;
   }
-  if (!sample_idx && n_res != npts) return COX_ERR_INVALID_ARG;
   const RelPose P = makeRelPose(pose_ref, pose_read);
   double sum_w = 0.0;
   uint64_t nc = 0;

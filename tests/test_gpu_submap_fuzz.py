@@ -9,12 +9,15 @@ one's reading submap and of its own, drawn samples) with the bars of tests/test_
 
 COX_FUZZ_SEEDS=N widens the sweep (the convention of tests/test_gpu_projective_fuzz.py)."""
 import os
+import zlib
 
 import numpy as np
 import pytest
 
+import reg_ref
 import submap_cases
 from coxgraph_amd.capi import Layer, RegPoints, Registration
+from test_reg_ref_cpu import check_evaluate
 from test_submap_ref_cpu import SAMPLER_SEEDS, ref_mesh, run_case  # noqa: F401  (ref_mesh is a module fixture)
 
 pytestmark = pytest.mark.gpu
@@ -67,6 +70,14 @@ def check_pair(hip, oracle, ph, po, readings, name):
         Hh, bh, ch, nh = gh.normal_eq(pr, pd)
         Ho, bo, co, no = go.normal_eq(pr, pd)
         assert nh == no and np.allclose(Hh, Ho, rtol=1e-9, atol=1e-9 * np.abs(Ho).max()) and abs(ch - co) <= 1e-9 * max(1.0, co), (name, what)
+        # and against the numpy restatement of the cost (tests/reg_ref.py), at a seeded pose of this pair the oracle
+        # comparison does not visit: yaw anywhere, up to two voxels of translation.  The isosurface weights are arbitrary
+        # floats, so only the order of their sum can differ: check_evaluate's (n + 2) 2^-53 |value|
+        rng = np.random.default_rng(zlib.crc32(f"{name} {what}".encode()))
+        pd2 = np.concatenate([rng.uniform(-2, 2, 3) * eh.voxel_size, rng.uniform(-np.pi, np.pi, 1)])
+        ev = reg_ref.evaluate(reg_ref.RefLayer(eh.voxel_size, *eh.download()), ph.download(), pr, pd2, gh.get_samples())
+        print(f"[pair {name} / {what}] reference at yaw {pd2[3]:+.2f}: {int(ev['has'].sum())} of {n_res} with a correspondence")
+        check_evaluate(gh.evaluate(pr, pd2), ev, False, (name, what, "reg_ref"))
 
 
 @pytest.mark.parametrize("seed", range(N_SEEDS))

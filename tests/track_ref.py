@@ -62,30 +62,24 @@ class RefLayer:
         pos = np.clip(np.searchsorted(self.keys, k), 0, len(self.keys) - 1)
         return self.keys[pos] == k, pos
 
-    def per_point(self, T, pts, stride=1, max_abs_distance=0.0):
-        """Steps 1-3 at the float32 pose T for scan pts [n,3]: dict(status uint8[n], pG[n,3], d[n], g[n,3]); NaN where the
-        matching status bit is clear."""
-        T = np.asarray(T, F)
-        pts = np.ascontiguousarray(pts, F).reshape(-1, 3)
-        n = len(pts)
-        status = np.zeros(n, np.uint8)
-        pG, d, g = np.full((n, 3), np.nan, F), np.full(n, np.nan, F), np.full((n, 3), np.nan, F)
-        ci = np.nonzero((np.arange(n) % stride == 0) & np.isfinite(pts).all(1))[0]
-        status[ci] = CONSIDERED
-        if len(ci) == 0:
-            return dict(status=status, pG=pG, d=d, g=g)
+    def cell(self, p):
+        """voxblox getVoxelsAndQVector at float32 positions p [m,3] in the layer's frame (shared with tests/reg_ref.py):
+        -> (valid bool[m], dd [k,8] corner distances and off [k,3] offsets of the k valid points).  Not valid: a coordinate
+        that is NaN, +-inf or beyond the packed keys, the block of the point missing, a block of the cell missing, a corner
+        of weight <= 0."""
+        p = np.ascontiguousarray(p, F).reshape(-1, 3)
+        sel = np.arange(len(p))
         with np.errstate(over="ignore", invalid="ignore"):
-            p = transform_points(T, pts[ci])
-            pG[ci] = p
             sc = (p * self.bs_inv).astype(F)
             ok = ((sc > F(-1048575.0)) & (sc < F(1048575.0))).all(1)  # index_in_range
-        ci, p, sc = ci[ok], p[ok], sc[ok]
+        sel, p, sc = sel[ok], p[ok], sc[ok]
         b = np.floor((sc + EPS).astype(F)).astype(np.int64)
         found, _ = self._find(b)  # the block of the point must exist
-        ci, p, b = ci[found], p[found], b[found]
-        if len(ci) == 0:
-            return dict(status=status, pG=pG, d=d, g=g)
-        # getVoxelsAndQVector: the voxel of the point, one down where the point lies below its centre
+        sel, p, b = sel[found], p[found], b[found]
+        valid = np.zeros(len(ok), bool)
+        if len(sel) == 0:
+            return valid, np.zeros((0, 8), F), np.zeros((0, 3), F)
+        # the voxel of the point, one down where the point lies below its centre
         origin = (b.astype(F) * self.bs).astype(F)
         rel = (p - origin).astype(F)
         v = np.clip(np.floor(((rel * self.vs_inv).astype(F) + EPS).astype(F)).astype(np.int64), 0, 15)
@@ -96,7 +90,7 @@ class RefLayer:
         v = v + 16 * under
         c0 = ((b.astype(F) * self.bs).astype(F) + ((v.astype(F) + F(0.5)) * self.vs).astype(F)).astype(F)
         off = ((p - c0).astype(F) * self.vs_inv).astype(F)
-        m = len(ci)
+        m = len(sel)
         dd, ww, all_blocks = np.zeros((m, 8), F), np.zeros((m, 8), F), np.ones(m, bool)
         for i in range(8):
             vv = v + np.array([(i >> 2) & 1, (i >> 1) & 1, i & 1])
@@ -108,9 +102,14 @@ class RefLayer:
             dd[:, i] = self.dist[pos, lin] if len(self.keys) else 0
             ww[:, i] = self.weight[pos, lin] if len(self.keys) else 0
         with np.errstate(invalid="ignore"):
-            valid = all_blocks & (ww > 0).all(1)  # isVoxelValid on all eight
-        ci, dd, off = ci[valid], dd[valid], off[valid]
-        m = len(ci)
+            good = all_blocks & (ww > 0).all(1)  # isVoxelValid on all eight
+        valid[sel[good]] = True
+        return valid, dd[good], off[good]
+
+    def value_and_gradient(self, dd, off):
+        """The interpolation table, the q vectors and their derivatives on cell()'s output: -> (val [k], grad [k,3] per
+        metre), float32 operation by operation."""
+        m = len(dd)
         # M . data, sequential float sums from 0, zero entries included
         md = np.zeros((m, 8), F)
         for r in range(8):
@@ -133,6 +132,26 @@ class RefLayer:
             return s
         val = dot(q)
         grad = np.stack([(dot(qx) * self.vs_inv).astype(F), (dot(qy) * self.vs_inv).astype(F), (dot(qz) * self.vs_inv).astype(F)], 1)
+        return val, grad
+
+    def per_point(self, T, pts, stride=1, max_abs_distance=0.0):
+        """Steps 1-3 at the float32 pose T for scan pts [n,3]: dict(status uint8[n], pG[n,3], d[n], g[n,3]); NaN where the
+        matching status bit is clear."""
+        T = np.asarray(T, F)
+        pts = np.ascontiguousarray(pts, F).reshape(-1, 3)
+        n = len(pts)
+        status = np.zeros(n, np.uint8)
+        pG, d, g = np.full((n, 3), np.nan, F), np.full(n, np.nan, F), np.full((n, 3), np.nan, F)
+        ci = np.nonzero((np.arange(n) % stride == 0) & np.isfinite(pts).all(1))[0]
+        status[ci] = CONSIDERED
+        if len(ci) == 0:
+            return dict(status=status, pG=pG, d=d, g=g)
+        with np.errstate(over="ignore", invalid="ignore"):
+            p = transform_points(T, pts[ci])
+            pG[ci] = p
+        valid, dd, off = self.cell(p)
+        ci = ci[valid]
+        val, grad = self.value_and_gradient(dd, off)
         if max_abs_distance > 0:
             keep = np.abs(val) <= F(max_abs_distance)
             ci, val, grad = ci[keep], val[keep], grad[keep]
