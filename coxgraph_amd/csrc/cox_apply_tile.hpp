@@ -143,7 +143,7 @@ __device__ __forceinline__ RayOfRecord ray_of_record(const RayArrays& R, u32 r) 
     typedef float F4 __attribute__((ext_vector_type(4)));
     const F4* q = reinterpret_cast<const F4*>(R.q + static_cast<size_t>(r) * 8u);
     const F4 q0 = q[0];
-    return RayOfRecord{F3{q0.x, q0.y, q0.z}, q0.w, q[1].x};
+    return RayOfRecord{F3{q0.x, q0.y, q0.z}, q0.w, R.q[static_cast<size_t>(r) * 8u + 4u]};  // (one word of the second half, not four)
   } else {
     return RayOfRecord{F3{R.px[r], R.py[r], R.pz[r]}, 0.0f, R.w[r]};
   }
@@ -154,6 +154,57 @@ __device__ __forceinline__ float sdf_of_record(const FrameParams& P, const RayOf
     return step_sdf(P, y.a, y.dist, gx, gy, gz);
   else
     return compute_sdf(P, y.a, gx, gy, gz);
+}
+
+// ---- phase 1 of a tile: classify its records -------------------------------------------------------------------------------------
+// Sum of the saturating weights and number of records per voxel (| dirty << 31 where a record does not fold), into LDS accumulators
+// of 1 << kTS voxels.  A record is two dependent round trips -- key and ray id, then the ray's line -- in front of a few operations and
+// three LDS atomics, and the tiles around the sensor hold 10^4 records and more for one workgroup.  Every thread keeps kD records in
+// flight, level by level: all kD keys and ray ids, then all kD ray lines, then the evaluations, with no branch between the loads.
+// Integer sums: exact in any order, so kD changes no result.  kFilter: the range belongs to a bucket; records of its other tiles
+// (and invalid keys) are passed over.
+// Measured at 5 cm: 2 and 4 in flight take the same time -- the largest tile is not bound by the round
+// trips per thread -- and 8 spills under the kernels' 64-register limit and loses a third; what the loop gained came from its shape.
+constexpr u32 kClassifyDepth = 2;  // records per thread in flight (k_apply_block, k_big_classify)
+template <bool kQ, u32 kTS, bool kFilter, u32 kD>
+__device__ __forceinline__ void classify_records(const FrameParams& P, const RayArrays& R, const u32* __restrict__ rec_key, const u32* __restrict__ rec_ray, u32 beg, u32 end,
+                                                 u32 tid, u32 tile, int gx0, int gy0, int gz0, u32* acc_sum, u32* acc_cnt) {
+  constexpr u32 kTV = 1u << kTS;
+  // (the range, the tile and its origin are the same for the whole workgroup: in scalar registers they leave the vector ones to the
+  // records in flight)
+  beg = uniform_u32(beg);
+  end = uniform_u32(end);
+  tile = uniform_u32(tile);
+  gx0 = static_cast<int>(uniform_u32(static_cast<u32>(gx0)));
+  gy0 = static_cast<int>(uniform_u32(static_cast<u32>(gy0)));
+  gz0 = static_cast<int>(uniform_u32(static_cast<u32>(gz0)));
+  for (u32 i0 = beg + tid; i0 < end; i0 += kD * kBT) {
+    // a record that is not there reads the last one of the range instead (and is passed over below): no branch between the loads
+    u32 k[kD], r[kD];
+#pragma unroll
+    for (u32 u = 0; u < kD; ++u) {
+      const u32 i = min(i0 + u * kBT, end - 1u);
+      k[u] = rec_key[i];
+      r[u] = rec_ray[i];
+    }
+    RayOfRecord y[kD];
+#pragma unroll
+    for (u32 u = 0; u < kD; ++u) y[u] = ray_of_record<kQ>(R, r[u]);
+    // No branch around a record that is not this tile's (a missing one, another tile of the bucket, an invalid key): it is evaluated
+    // like the others and adds zero to a voxel of the tile.  With its evaluation inside a branch the compiler moves the record's
+    // line load in there as well, behind a wait for all the others: a third round trip.
+#pragma unroll
+    for (u32 u = 0; u < kD; ++u) {
+      const bool mine = i0 + u * kBT < end && (!kFilter || (k[u] >> kTS) == tile);
+      const u32 lin = k[u] & (kTV - 1u);
+      const float sdf = sdf_of_record<kQ>(P, y[u], gx0 + static_cast<int>(lin & 15u), gy0 + static_cast<int>((lin >> 4) & 15u), gz0 + static_cast<int>(lin >> 8));
+      const float uw = update_weight(P, sdf, y[u].w);
+      bool fold = mine && foldable_update(P, sdf, uw);
+      if (fold && atomicAdd(&acc_sum[lin], static_cast<u32>(uw)) >= (1u << 30)) fold = false;  // the sum must stay an exact u32
+      atomicAdd(&acc_cnt[lin], mine ? 1u : 0u);
+      if (mine && !fold) atomicOr(&acc_cnt[lin], 0x80000000u);
+    }
+  }
 }
 
 // ---- large tiles: phase 1 by the whole chip ------------------------------------------------------------------------------------
@@ -232,25 +283,7 @@ __global__ void __launch_bounds__(kBT) __attribute__((amdgpu_waves_per_eu(8, 8))
       acc_cnt[tid] = 0;
     }
     __syncthreads();
-    for (u32 i0 = beg + tid; i0 < end; i0 += 2 * kBT) {  // (k_apply_block's phase 1)
-      const u32 i1 = i0 + kBT;
-      const bool has1 = i1 < end;
-      const u32 k0 = rec_key[i0], r0 = rec_ray[i0];
-      const u32 k1 = has1 ? rec_key[i1] : 0u, r1 = has1 ? rec_ray[i1] : r0;
-      const RayOfRecord y0 = ray_of_record<kQ>(R, r0), y1 = ray_of_record<kQ>(R, r1);
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        if (u == 1 && !has1) break;
-        const u32 lin = (u ? k1 : k0) & (kTileVox - 1u);
-        const RayOfRecord& y = u ? y1 : y0;
-        const float sdf = sdf_of_record<kQ>(P, y, info.x + static_cast<int>(lin & 15u), info.y + static_cast<int>(lin >> 4), gz);
-        const float uw = update_weight(P, sdf, y.w);
-        bool fold = foldable_update(P, sdf, uw);
-        if (fold && atomicAdd(&acc_sum[lin], static_cast<u32>(uw)) >= (1u << 30)) fold = false;
-        atomicAdd(&acc_cnt[lin], 1u);
-        if (!fold) atomicOr(&acc_cnt[lin], 0x80000000u);
-      }
-    }
+    classify_records<kQ, kTileShift, false, kClassifyDepth>(P, R, rec_key, rec_ray, beg, end, tid, tile, info.x, info.y, gz, acc_sum, acc_cnt);
     __syncthreads();
     if (tid < kTileVox) {
       const u32 cv = acc_cnt[tid];
@@ -340,26 +373,7 @@ __global__ void __launch_bounds__(kBT) __attribute__((amdgpu_waves_per_eu(8, 8))
     __syncthreads();
     if (split && tid == 0) big.of_tile[tile] = 0;  // (behind the barrier: every thread has read the slot) ... and the slot table
     // ---- 1. classify --------------------------------------------------------------------------------------------------
-    for (u32 i0 = beg + tid; i0 < (split ? beg : end); i0 += 2 * kBT) {  // two records per thread in flight: the gathers are latency-bound
-      const u32 i1 = i0 + kBT;
-      const bool has1 = i1 < end;
-      const u32 k0 = rec_key[i0], r0 = rec_ray[i0];
-      const u32 k1 = has1 ? rec_key[i1] : 0u, r1 = has1 ? rec_ray[i1] : r0;
-      const RayOfRecord y0 = ray_of_record<kQ>(R, r0), y1 = ray_of_record<kQ>(R, r1);
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        if (u == 1 && !has1) break;
-        if (kBucket && ((u ? k1 : k0) >> kTS) != tile) continue;  // another tile of the bucket (or an invalid key)
-        const u32 lin = (u ? k1 : k0) & (kTV - 1u);
-        const RayOfRecord& y = u ? y1 : y0;
-        const float sdf = sdf_of_record<kQ>(P, y, info.x + static_cast<int>(lin & 15u), info.y + static_cast<int>((lin >> 4) & 15u), gz0 + static_cast<int>(lin >> 8));
-        const float uw = update_weight(P, sdf, y.w);
-        bool fold = foldable_update(P, sdf, uw);
-        if (fold && atomicAdd(&acc_sum[lin], static_cast<u32>(uw)) >= (1u << 30)) fold = false;  // the sum must stay an exact u32
-        atomicAdd(&acc_cnt[lin], 1u);
-        if (!fold) atomicOr(&acc_cnt[lin], 0x80000000u);
-      }
-    }
+    classify_records<kQ, kTS, kBucket, kClassifyDepth>(P, R, rec_key, rec_ray, beg, split ? beg : end, tid, tile, info.x, info.y, gz0, acc_sum, acc_cnt);
     __syncthreads();
     // ---- 2. fold what folds (thread = voxel) ----------------------------------------------------------------------------
     {

@@ -78,10 +78,12 @@ struct RecordView {
   const u32* d_n;
 };
 
+__device__ __forceinline__ u32 rgba_wire_order(u32 v) {  // v: little endian r | g<<8 | b<<16 | a<<24
+  return ((v >> 24) & 255u) | (((v >> 16) & 255u) << 8) | (((v >> 8) & 255u) << 16) | ((v & 255u) << 24);
+}
 __device__ __forceinline__ u32 pack_rgba_wire(const uint8_t* rgba, u32 i) {
   if (!rgba) return 0u;
-  const u32 v = reinterpret_cast<const u32*>(rgba)[i];  // little endian: r | g<<8 | b<<16 | a<<24
-  return ((v >> 24) & 255u) | (((v >> 16) & 255u) << 8) | (((v >> 8) & 255u) << 16) | ((v & 255u) << 24);
+  return rgba_wire_order(reinterpret_cast<const u32*>(rgba)[i]);
 }
 // isPointValid.  Non-finite points (which voxblox_ros filters out before the integrator, and on which upstream's
 // float -> int64 index casts are undefined) are defined as invalid here and in the oracle.

@@ -348,6 +348,10 @@ __global__ void __launch_bounds__(256) k_bundle_merge(const FrameParams* __restr
   const u32 np2 = P.np2;
   const float* __restrict__ xyz = P.xyz;
   const uint8_t* __restrict__ rgba = P.rgba;
+  typedef const float __attribute__((address_space(1))) * GlobalF32;
+  typedef const u32 __attribute__((address_space(1))) * GlobalU32;
+  const GlobalF32 gxyz = (GlobalF32)xyz;  // (device memory: see the gather below)
+  const GlobalU32 grgba = (GlobalU32)rgba;
   const u32 spar = uniform_u32(V.info->parity & 1u);
   const u32* __restrict__ skey = V.key[spar];
   const u32* __restrict__ sval = V.val[spar];
@@ -362,10 +366,11 @@ __global__ void __launch_bounds__(256) k_bundle_merge(const FrameParams* __restr
   for (u32 task = uniform_u32(tid >> 6); task < 2 * n_bundles; task += nthreads >> 6) {
     const u32 m = task >> 1;
     const bool colour_wave = (task & 1u) != 0;
+    // The loads of a task in as few dependent levels as they have: both bundle starts together (the last bundle reads its own start
+    // twice instead of branching around the second load), then the class of the bundle and the points of the first two chunks.
     const u32 begin = uniform_u32(bstart[m]);
-    const u32 end = uniform_u32((m + 1 < n_bundles) ? bstart[m + 1] : n_valid);
-    const bool clearing = uniform_u32(skey[begin]) >= np2;
-    if (!colour_wave && lane == 0) atomicMax(&cnt->shard[m & 63u][kShMaxBundle], end - begin);
+    const u32 next_start = uniform_u32(bstart[min(m + 1u, n_bundles - 1u)]);
+    const u32 end = (m + 1 < n_bundles) ? next_start : n_valid;
     if (colour_wave && rgba == nullptr) {  // no colours: Color() stays (0,0,0,0)
       if (lane == 0) {
         R.color[m] = 0u;
@@ -373,6 +378,34 @@ __global__ void __launch_bounds__(256) k_bundle_merge(const FrameParams* __restr
       }
       continue;
     }
+    // Software pipeline of the chunk loop: while the chain of chunk k runs, the points of chunk k + 1 (gathered through sv_b, which
+    // arrived during chunk k - 1) and the sorted values of chunk k + 2 are in flight, so neither dependent level of the gather sits
+    // between two chains.  All of it is set here, per task: nothing is carried from one task of the grid-stride loop into the next.
+    // A load is issued only for i < end (never sval at or beyond end); a clearing bundle that is done drops what is in flight.
+    // The gather only loads (the colour's bytes are put in wire order where it is used: an operation on the loaded value here would
+    // wait for it in front of the chain), and it loads through global pointers: a pointer read from FrameParams is a generic one to
+    // the compiler, and a flat load in flight makes every LDS wait of the chain a wait for that load as well.
+    auto gather = [&](bool has, u32 sv, float& x, float& y, float& z, u32& c) {
+      x = 0.0f;
+      y = 0.0f;
+      z = 0.0f;
+      c = 0u;
+      if (has) {
+        const u32 idx = mixed_index(sv, P.n_points);
+        x = gxyz[3 * idx];
+        y = gxyz[3 * idx + 1];
+        z = gxyz[3 * idx + 2];
+        if (colour_wave) c = grgba[idx];
+      }
+    };
+    const u32 key0 = skey[begin];
+    const u32 sv_a = (begin + lane < end) ? sval[begin + lane] : 0u;
+    u32 sv_b = (begin + 64u + lane < end) ? sval[begin + 64u + lane] : 0u;  // sorted values one chunk ahead of the points in flight
+    float npx, npy, npz;                                                    // the next chunk's points
+    u32 ncol;
+    gather(begin + lane < end, sv_a, npx, npy, npz, ncol);
+    const bool clearing = uniform_u32(key0) >= np2;
+    if (!colour_wave && lane == 0) atomicMax(&cnt->shard[m & 63u][kShMaxBundle], end - begin);
     float val = 0.0f;  // this lane's component of the running mean / colour channel
     float W = 0.0f;    // uniform
     u64 key = 0;
@@ -380,16 +413,12 @@ __global__ void __launch_bounds__(256) k_bundle_merge(const FrameParams* __restr
     for (u32 base = begin; base < end && !done; base += 64) {
       const u32 i = base + lane;
       const u32 cnt_in = min(64u, end - base);
-      float px = 0.0f, py = 0.0f, pz = 0.0f, w = 0.0f;
-      u32 col = 0;
-      if (i < end) {
-        const u32 idx = mixed_index(sval[i], P.n_points);
-        px = xyz[3 * idx];
-        py = xyz[3 * idx + 1];
-        pz = xyz[3 * idx + 2];
-        w = voxel_weight(P, F3{px, py, pz});
-        if (colour_wave) col = pack_rgba_wire(rgba, idx);
-      }
+      const float px = npx, py = npy, pz = npz;
+      const u32 col = rgba_wire_order(ncol);
+      const float w = (i < end) ? voxel_weight(P, F3{px, py, pz}) : 0.0f;
+      // ahead of the chain: the next chunk's points and the sorted values of the chunk behind it
+      gather(i + 64u < end, sv_b, npx, npy, npz, ncol);
+      sv_b = (i + 128u < end) ? sval[i + 128u] : 0u;
       if (base == begin && !colour_wave) {
         const F3 pg = transform_point(P, F3{readlane_f32(px, 0), readlane_f32(py, 0), readlane_f32(pz, 0)});
         key = pack_key(grid_index(pg.x * P.voxel_size_inv), grid_index(pg.y * P.voxel_size_inv), grid_index(pg.z * P.voxel_size_inv));
