@@ -1623,6 +1623,153 @@ class StereoMatcher(_Handle):
         return out
 
 
+# ---- aligning two submaps without a prior (include/coxgraph_hip_align.h) -----
+ALIGN_Q, ALIGN_MAX_CANDIDATES, ALIGN_MAX_KEEP, ALIGN_MAX_LEVELS = 1024, 1 << 20, 64, 16
+
+
+class AlignConfig(C.Structure):
+    """cox_align_config."""
+    _fields_ = [("inlier_distance", C.c_float), ("pad", C.c_uint32), ("no_correspondence_cost", C.c_double)]
+
+
+class AlignScore(C.Structure):
+    """cox_align_score."""
+    _fields_ = [("score", C.c_uint64), ("n_corr", C.c_uint32), ("n_inlier", C.c_uint32), ("cost", C.c_double)]
+
+
+class AlignSearchConfig(C.Structure):
+    """cox_align_search_config."""
+    _fields_ = [("center", C.c_double * 4), ("half_extent", C.c_double * 4), ("step", C.c_double * 4), ("inlier_distance", C.c_float), ("tau_min", C.c_float),
+                ("levels", C.c_uint32), ("keep", C.c_uint32), ("min_corr", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class AlignLevel(C.Structure):
+    """cox_align_level."""
+    _fields_ = [("n_candidates", C.c_uint64), ("step", C.c_double * 4), ("inlier_distance", C.c_float), ("n_kept", C.c_uint32),
+                ("kept_index", C.c_uint32 * ALIGN_MAX_KEEP), ("kept_pose", C.c_double * (4 * ALIGN_MAX_KEEP)), ("kept_score", AlignScore * ALIGN_MAX_KEEP)]
+
+
+ALIGN_SCORE_DTYPE = np.dtype([("score", np.uint64), ("n_corr", np.uint32), ("n_inlier", np.uint32), ("cost", np.float64)])
+assert ALIGN_SCORE_DTYPE.itemsize == 24 == C.sizeof(AlignScore)
+
+
+def align_config(eng, **cfg):
+    """cox_align_config_default with overrides."""
+    return _config(eng, AlignConfig, "align_config_default", cfg)
+
+
+def _pose4(p):
+    p = np.ascontiguousarray(p, np.float64)
+    assert p.shape == (4,)
+    return p
+
+
+def align_grid(eng, center, half_extent, step):
+    """cox_align_grid: float64 [n,4] poses x, y, z, yaw around center, x slowest and yaw fastest.  Needs no GPU."""
+    c, h, s = _pose4(center), _pose4(half_extent), _pose4(step)
+    n = C.c_uint64()
+    eng.call("align_grid", _fp(c), _fp(h), _fp(s), None, C.c_uint64(0), C.byref(n))
+    out = np.zeros((int(n.value), 4), np.float64)
+    eng.call("align_grid", _fp(c), _fp(h), _fp(s), _fp(out), C.c_uint64(len(out)), C.byref(n))
+    return out
+
+
+def align_select(eng, scores, min_corr, keep):
+    """cox_align_select on a structured array of ALIGN_SCORE_DTYPE: the kept indices (uint32), best first.  Needs no GPU."""
+    scores = np.ascontiguousarray(scores, ALIGN_SCORE_DTYPE)
+    idx, n = np.zeros(ALIGN_MAX_KEEP, np.uint32), C.c_uint32()
+    eng.call("align_select", _fp(scores), C.c_uint64(len(scores)), C.c_uint32(min_corr), C.c_uint32(keep), _fp(idx), C.byref(n))
+    return idx[:int(n.value)].copy()
+
+
+class SubmapAligner(_Handle):
+    """Scores candidate reference poses of one (reference points, reading layer) pair and searches them coarse to fine
+    (cox_align_t): cfg are fields of cox_align_config."""
+    _destroy = "align_destroy"
+
+    def _guard(self, name):
+        """As _Handle._guard with _borrows = ("ref", "reading")."""
+        if not self.ref.h or not self.reading.h:
+            raise CoxError(-1, name + " (the layer is closed)")
+        return self.h
+
+    def __init__(self, eng, ref_points, reading_layer, **cfg):
+        self.eng, self.ref, self.reading = eng, ref_points, reading_layer
+        self.cfg = align_config(eng, **cfg)
+        self.samples = None
+        self.h = C.c_void_p()
+        eng.call("align_create", ref_points.h, reading_layer.h, C.byref(self.cfg), C.byref(self.h))
+
+    def set_samples(self, sample_idx):
+        """The points of a sweep as indices into the reference set (repeats allowed); None: all points in order."""
+        if sample_idx is None:
+            self._call("align_set_samples", None, C.c_uint64(0))
+            self.samples = None
+            return
+        si = np.ascontiguousarray(sample_idx, np.uint32)
+        self._call("align_set_samples", _fp(si), C.c_uint64(si.shape[0]))
+        self.samples = si
+
+    def sweep(self, poses_ref, pose_read=(0, 0, 0, 0), inlier_distance=None):
+        """cox_align_sweep: one record of ALIGN_SCORE_DTYPE per candidate reference pose [M,4]."""
+        pr = np.ascontiguousarray(poses_ref, np.float64).reshape(-1, 4)
+        out = np.zeros(len(pr), ALIGN_SCORE_DTYPE)
+        tau = self.cfg.inlier_distance if inlier_distance is None else inlier_distance
+        self._call("align_sweep", _fp(_pose4(pose_read)), _fp(pr), C.c_uint64(len(pr)), C.c_float(tau), _fp(out))
+        return out
+
+    def search(self, center, half_extent, step, levels=4, keep=8, min_corr=0, tau_min=None, pose_read=(0, 0, 0, 0), inlier_distance=None, trace=False,
+               refine=False):
+        """cox_align_search: dict(poses [k,4] and scores [k] of the last level's kept candidates, best first; n_found; best = poses[0]
+        or None).  trace=True adds levels = [dict(n_candidates, inlier_distance, step, kept_index, kept_pose, kept_score)].
+        refine=True polishes the best pose with the registration cost (Registration.normal_eq under
+        posegraph.trust_region_minimize, the reading pose fixed) and adds refined (pose), cost_before, cost_after."""
+        tau = self.cfg.inlier_distance if inlier_distance is None else inlier_distance
+        sc = AlignSearchConfig((C.c_double * 4)(*_pose4(center)), (C.c_double * 4)(*_pose4(half_extent)), (C.c_double * 4)(*_pose4(step)), tau,
+                               tau / 4 if tau_min is None else tau_min, levels, keep, min_corr, 0)
+        pose_read = _pose4(pose_read)
+        k = max(1, min(int(keep), ALIGN_MAX_KEEP))
+        poses, scores, n = np.zeros((k, 4), np.float64), np.zeros(k, ALIGN_SCORE_DTYPE), C.c_uint32()
+        tr = (AlignLevel * (int(levels) + 1))() if trace and 0 <= levels <= ALIGN_MAX_LEVELS else None
+        self._call("align_search", _fp(pose_read), C.byref(sc), _fp(poses), _fp(scores), C.byref(n), tr)
+        n = int(n.value)
+        out = dict(poses=poses[:n], scores=scores[:n], n_found=n, best=poses[0].copy() if n else None)
+        if tr is not None:
+            out["levels"] = []
+            for t in tr:
+                if t.n_candidates == 0:
+                    break
+                kk = int(t.n_kept)
+                rec = np.frombuffer(t.kept_score, ALIGN_SCORE_DTYPE)[:kk].copy()
+                out["levels"].append(dict(n_candidates=int(t.n_candidates), inlier_distance=float(t.inlier_distance), step=np.array(t.step[:]),
+                                          kept_index=np.array(t.kept_index[:kk], np.uint32), kept_pose=np.array(t.kept_pose[:4 * kk]).reshape(kk, 4),
+                                          kept_score=rec))
+        if refine and n:
+            out.update(self.refine(out["best"], pose_read))
+        return out
+
+    def refine(self, pose_ref, pose_read=(0, 0, 0, 0)):
+        """The registration cost minimised over the reference pose from pose_ref: dict(refined, cost_before, cost_after).  The
+        minimiser takes monotonic steps only, so cost_after <= cost_before."""
+        from . import posegraph
+        pose_read = _pose4(pose_read)
+        reg = Registration(self.eng, self.ref, self.reading, self.cfg.no_correspondence_cost)
+        try:
+            def evaluate(x):
+                H, b, cost, _ = reg.normal_eq(x, pose_read, self.samples)
+                return cost, b[:4].copy(), H[:4, :4].copy()
+            x, summary = posegraph.trust_region_minimize(evaluate, _pose4(pose_ref), lambda x, d: x + d)
+        finally:
+            reg.close()
+        return dict(refined=x, cost_before=float(summary["initial_cost"]), cost_after=float(summary["final_cost"]))
+
+    def kernel_time(self, reset=False):
+        """(milliseconds of the sweeps' kernels, sweeps) since creation or the last reset."""
+        ms, n = C.c_double(), C.c_uint64()
+        self._call("align_kernel_time", C.byref(ms), C.byref(n), C.c_int(int(reset)))
+        return float(ms.value), int(n.value)
+
+
 # ---- wire-format helpers (voxblox_msgs/Block data words) -----------------------------------------
 def words_to_fields(vox):
     """uint32[...,3] wire words -> (distance f32, weight f32, rgba u8[...,4])."""

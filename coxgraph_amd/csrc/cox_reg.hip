@@ -21,38 +21,11 @@
 #include "cox_device.hpp"
 #include "cox_host.hpp"
 #include "cox_interp.hpp"
+#include "cox_reg.hpp"
 
 using namespace cox;
 
 using ReadingView = LayerView;
-
-// relative pose reading<-reference: float for the per-point transform, double for the Jacobians
-struct RelPose {
-  float R[9];
-  float t[3];
-  double cf, sf, cr, sr;
-  double tf[3], tr[3];
-};
-
-static RelPose make_rel_pose(const double ref[4], const double read[4]) {
-  RelPose P;
-  P.cf = std::cos(ref[3]);
-  P.sf = std::sin(ref[3]);
-  P.cr = std::cos(read[3]);
-  P.sr = std::sin(read[3]);
-  for (int k = 0; k < 3; ++k) {
-    P.tf[k] = ref[k];
-    P.tr[k] = read[k];
-  }
-  const double c = P.cr * P.cf + P.sr * P.sf, s = P.cr * P.sf - P.sr * P.cf;
-  const double Rd[9] = {c, -s, 0, s, c, 0, 0, 0, 1};
-  for (int i = 0; i < 9; ++i) P.R[i] = static_cast<float>(Rd[i]);
-  const double dx = ref[0] - read[0], dy = ref[1] - read[1], dz = ref[2] - read[2];
-  P.t[0] = static_cast<float>(P.cr * dx + P.sr * dy);
-  P.t[1] = static_cast<float>(-P.sr * dx + P.cr * dy);
-  P.t[2] = static_cast<float>(dz);
-  return P;
-}
 
 struct PointResult {
   double r;
@@ -70,26 +43,14 @@ __device__ __forceinline__ PointResult reg_point(const ReadingView& L, const Rel
   o.r = static_cast<double>(pw) * no_corr_cost;
 #pragma unroll
   for (int k = 0; k < 8; ++k) o.J[k] = 0.0;
-  const float pos[3] = {(P.R[0] * px + P.R[1] * py) + P.R[2] * pz + P.t[0], (P.R[3] * px + P.R[4] * py) + P.R[5] * pz + P.t[1],
-                        (P.R[6] * px + P.R[7] * py) + P.R[8] * pz + P.t[2]};
-  float sc[3];
-  if (!block_scaled(L, pos, sc)) return o;
-  int b[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) b[k] = grid_index(sc[k]);
-  if (ht_find(L.ht_keys, L.ht_mask, pack_key(b[0], b[1], b[2])) == kInvalid) return o;  // block of the point must exist
-  float d[8], wv[8], off[3];
-  if (!interp_cell(L, pos, b, HtPool{L}, d, wv, off)) return o;
-  float md[8];
-  interp_table_apply(d, md);
+  float md[8], off[3];
+  if (!reg_cell(L, P.R, P.t, px, py, pz, md, off)) return o;
   const float dx = off[0], dy = off[1], dz = off[2];
-  const float q[8] = {1.0f, dx, dy, dz, dx * dy, dy * dz, dz * dx, dx * dy * dz};
   const float qx[8] = {0, 1, 0, 0, dy, 0, dz, dy * dz};
   const float qy[8] = {0, 0, 1, 0, dx, dz, 0, dz * dx};
   const float qz[8] = {0, 0, 0, 1, 0, dy, dx, dx * dy};
-  float val = 0.0f, gxf = 0.0f, gyf = 0.0f, gzf = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) val += q[i] * md[i];
+  const float val = reg_value(md, off);
+  float gxf = 0.0f, gyf = 0.0f, gzf = 0.0f;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     gxf += qx[i] * md[i];
