@@ -1447,6 +1447,10 @@ static const void* host_pointer_device_view(const void* p) {
   if (a.type != hipMemoryTypeHost) return nullptr;
   return a.devicePointer ? a.devicePointer : p;
 }
+// what k_copy_from_host is told about one array of `bytes` (a multiple of 4; both addresses 16-byte aligned): whole 16 bytes, then words
+static inline HostSegment host_segment(void* dst, const void* src_dev, size_t bytes) {
+  return HostSegment{static_cast<U32x4*>(dst), static_cast<const U32x4*>(src_dev), bytes / 16, static_cast<u32>((bytes & 15u) / 4)};
+}
 // one or two arrays (bytes a multiple of 4) from pinned host memory, seen by the device at src_dev_*, to dst_* on stream s
 static int copy_pinned_to_device(const cox_integrator* I, void* dst_a, const void* src_a, const void* src_dev_a, size_t bytes_a, void* dst_b, const void* src_b,
                                  const void* src_dev_b, size_t bytes_b, hipStream_t s) {
@@ -1460,9 +1464,8 @@ static int copy_pinned_to_device(const cox_integrator* I, void* dst_a, const voi
     if (two) COX_HIP(hipMemcpyAsync(dst_b, src_b, bytes_b, hipMemcpyHostToDevice, s));
     return COX_OK;
   }
-  HostSegment A{static_cast<U32x4*>(dst_a), static_cast<const U32x4*>(src_dev_a), bytes_a / 16, static_cast<u32>((bytes_a & 15u) / 4)};
-  HostSegment B{nullptr, nullptr, 0, 0};
-  if (two) B = HostSegment{static_cast<U32x4*>(dst_b), static_cast<const U32x4*>(src_dev_b), bytes_b / 16, static_cast<u32>((bytes_b & 15u) / 4)};
+  const HostSegment A = host_segment(dst_a, src_dev_a, bytes_a);
+  const HostSegment B = two ? host_segment(dst_b, src_dev_b, bytes_b) : HostSegment{nullptr, nullptr, 0, 0};
   hipLaunchKernelGGL(k_copy_from_host, dim3(groups), dim3(256), 0, s, A, B);
   return COX_OK;
 }
@@ -1578,13 +1581,19 @@ int cox_integrator_wait_inputs(cox_integrator_t* I) {
 }
 
 // depth image (device) -> point list in staging set k on stream s; the point count lands in d_depth_n[k]
-static void convert_depth(cox_integrator* I, int k, const float* depth_dev, const uint8_t* rgba_dev, int w, int h, const float K[4], hipStream_t s) {
+// tiles of kDepthTile pixels in an image of n, and the words of tile_sums the two kernels use (one workgroup per tile: the grid)
+static inline u32 depth_tiles(u32 n) { return std::max<u32>(1, (n + kDepthTile - 1) / kDepthTile); }
+// the two launches of the depth front end; grid 0: one workgroup per tile (both kernels stride over the tiles with any grid)
+static void launch_depth_convert(const float* depth_dev, const uint8_t* rgba_dev, int w, int h, const float K[4], u32 grid, u32* tile_sums, float* xyz,
+                                 uint8_t* rgba_out, u32* n_out, hipStream_t s) {
   const u32 n = static_cast<u32>(w) * static_cast<u32>(h);
-  const dim3 gt(std::max<u32>(1, (n + kDepthTile - 1) / kDepthTile));
-  u32* tile_sums = I->depth_flag + static_cast<size_t>(k) * (I->pcap / kDepthTile + 1);  // one set per staging set: consecutive frames convert on different streams
+  const dim3 gt(grid ? grid : depth_tiles(n));
   hipLaunchKernelGGL(k_depth_count, gt, dim3(256), 0, s, depth_dev, n, tile_sums);
-  hipLaunchKernelGGL(k_depth_points, gt, dim3(256), 0, s, depth_dev, rgba_dev, w, h, K[0], K[1], K[2], K[3], tile_sums, I->own_xyz[k], I->own_rgba[k],
-                     I->d_depth_n + k);
+  hipLaunchKernelGGL(k_depth_points, gt, dim3(256), 0, s, depth_dev, rgba_dev, w, h, K[0], K[1], K[2], K[3], tile_sums, xyz, rgba_out, n_out);
+}
+static void convert_depth(cox_integrator* I, int k, const float* depth_dev, const uint8_t* rgba_dev, int w, int h, const float K[4], hipStream_t s) {
+  u32* tile_sums = I->depth_flag + static_cast<size_t>(k) * (I->pcap / kDepthTile + 1);  // one set per staging set: consecutive frames convert on different streams
+  launch_depth_convert(depth_dev, rgba_dev, w, h, K, 0, tile_sums, I->own_xyz[k], I->own_rgba[k], I->d_depth_n + k, s);
 }
 
 int cox_integrate_depth_dev(cox_integrator_t* I, const float T_G_C[7], const float* depth_dev, const uint8_t* rgba_dev, int w, int h, const float K[4]) {
@@ -1780,6 +1789,97 @@ int cox_selftest_scan_small(int device, const uint32_t* in_a, const uint32_t* in
     return COX_OK;
   }();
   (void)hipFree(d);
+  return st;
+}
+
+// words of a 64-word guard on the device that no longer hold the sentinel
+constexpr u32 kSelftestGuard = 64;
+static int selftest_guard_touched(const u32* d_guard, u32 sentinel, uint32_t* touched) {
+  u32 g[kSelftestGuard];
+  COX_HIP(hipMemcpy(g, d_guard, sizeof(g), hipMemcpyDeviceToHost));
+  *touched = 0;
+  for (u32 v : g) *touched += v != sentinel ? 1u : 0u;
+  return COX_OK;
+}
+
+// The depth front end on a caller-supplied image (tests/test_gpu_frontend.py), launched by the code convert_depth launches it with.
+int cox_selftest_depth_points(int device, const float* depth, const uint8_t* rgba, int w, int h, const float K[4], uint32_t grid, int want_rgba,
+                              uint32_t sentinel, float* xyz_out, uint8_t* rgba_out, uint32_t* tile_sums_out, uint32_t* n_out, uint32_t guard_touched[3]) {
+  COX_ENTRY();
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return COX_ERR_NO_DEVICE;
+  if (!depth || !K || w <= 0 || h <= 0 || static_cast<uint64_t>(w) * h > (1ull << 24) || grid > 65535u || !xyz_out || !rgba_out || !tile_sums_out ||
+      !n_out || !guard_touched)
+    return COX_ERR_INVALID_ARG;
+  COX_HIP(hipSetDevice(device));
+  // one allocation of words: depth, colours in, then every output with its guard behind it, the count last
+  const size_t n = static_cast<size_t>(w) * h, tiles = depth_tiles(static_cast<u32>(n)), G = kSelftestGuard;
+  const size_t o_rgba_in = n, o_xyz = 2 * n, o_rgba = o_xyz + 3 * n + G, o_tiles = o_rgba + n + G, o_n = o_tiles + tiles + G, words = o_n + 1;
+  DevBuf<u32> buf;
+  COX_TRY(buf.alloc(words));
+  u32* d = buf.p;
+  COX_HIP(hipMemcpy(d, depth, n * sizeof(float), hipMemcpyHostToDevice));
+  if (rgba) COX_HIP(hipMemcpy(d + o_rgba_in, rgba, n * 4, hipMemcpyHostToDevice));
+  COX_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d + o_xyz), static_cast<int>(sentinel), words - o_xyz));
+  COX_HIP(hipDeviceSynchronize());
+  launch_depth_convert(reinterpret_cast<const float*>(d), rgba ? reinterpret_cast<const uint8_t*>(d + o_rgba_in) : nullptr, w, h, K, grid, d + o_tiles,
+                       reinterpret_cast<float*>(d + o_xyz), want_rgba ? reinterpret_cast<uint8_t*>(d + o_rgba) : nullptr, d + o_n, nullptr);
+  COX_HIP(hipGetLastError());
+  COX_HIP(hipDeviceSynchronize());
+  COX_HIP(hipMemcpy(xyz_out, d + o_xyz, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+  COX_HIP(hipMemcpy(rgba_out, d + o_rgba, n * 4, hipMemcpyDeviceToHost));
+  COX_HIP(hipMemcpy(tile_sums_out, d + o_tiles, tiles * sizeof(u32), hipMemcpyDeviceToHost));
+  COX_HIP(hipMemcpy(n_out, d + o_n, sizeof(u32), hipMemcpyDeviceToHost));
+  COX_TRY(selftest_guard_touched(d + o_xyz + 3 * n, sentinel, &guard_touched[0]));
+  COX_TRY(selftest_guard_touched(d + o_rgba + n, sentinel, &guard_touched[1]));
+  COX_TRY(selftest_guard_touched(d + o_tiles + tiles, sentinel, &guard_touched[2]));
+  return COX_OK;
+}
+
+// k_copy_from_host on caller-supplied arrays put into pinned host memory, with the segments copy_pinned_to_device builds.
+int cox_selftest_copy_from_host(int device, const uint32_t* a, uint64_t words_a, const uint32_t* b, uint64_t words_b, int groups, uint32_t sentinel,
+                                uint32_t* out_a, uint32_t* out_b, uint32_t guard_touched[2]) {
+  COX_ENTRY();
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return COX_ERR_NO_DEVICE;
+  constexpr uint64_t kMaxWords = 1ull << 24;
+  if (groups < 1 || groups > 1024 || words_a > kMaxWords || words_b > kMaxWords || !guard_touched || (words_a && (!a || !out_a)) || (!b && words_b) ||
+      (words_b && !out_b))
+    return COX_ERR_INVALID_ARG;
+  COX_HIP(hipSetDevice(device));
+  // both sides: a, then b from the next multiple of 16 bytes on; on the device a guard behind each
+  const size_t G = kSelftestGuard, a4 = (words_a + 3) & ~static_cast<size_t>(3), b4 = (words_b + 3) & ~static_cast<size_t>(3);
+  const size_t o_b = a4 + G, words = o_b + b4 + G;
+  u32* pinned = nullptr;
+  COX_HIP(hipHostMalloc(reinterpret_cast<void**>(&pinned), (a4 + b4 + 4) * sizeof(u32), hipHostMallocDefault));
+  const int st = [&]() -> int {
+    DevBuf<u32> buf;
+    COX_TRY(buf.alloc(words));
+    u32* d = buf.p;
+    if (words_a) memcpy(pinned, a, words_a * sizeof(u32));
+    if (words_b) memcpy(pinned + a4, b, words_b * sizeof(u32));
+    const u32* pinned_dev = static_cast<const u32*>(host_pointer_device_view(pinned));
+    if (!pinned_dev || (reinterpret_cast<uintptr_t>(pinned_dev) & 15u) || (reinterpret_cast<uintptr_t>(d) & 15u)) return COX_ERR_INTERNAL;
+    COX_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d), static_cast<int>(sentinel), words));
+    COX_HIP(hipDeviceSynchronize());
+    const HostSegment A = host_segment(d, pinned_dev, words_a * sizeof(u32));
+    const HostSegment B = b ? host_segment(d + o_b, pinned_dev + a4, words_b * sizeof(u32)) : HostSegment{nullptr, nullptr, 0, 0};
+    hipLaunchKernelGGL(k_copy_from_host, dim3(groups), dim3(256), 0, nullptr, A, B);
+    COX_HIP(hipGetLastError());
+    COX_HIP(hipDeviceSynchronize());
+    // (the padding words between an array's end and its guard count as guard: nothing may write them either)
+    if (words_a) COX_HIP(hipMemcpy(out_a, d, words_a * sizeof(u32), hipMemcpyDeviceToHost));
+    if (words_b) COX_HIP(hipMemcpy(out_b, d + o_b, words_b * sizeof(u32), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 2; ++k) {
+      const size_t end = k ? o_b + words_b : words_a, stop = k ? words : o_b;
+      std::vector<u32> g(stop - end);
+      COX_HIP(hipMemcpy(g.data(), d + end, g.size() * sizeof(u32), hipMemcpyDeviceToHost));
+      guard_touched[k] = 0;
+      for (u32 v : g) guard_touched[k] += v != sentinel ? 1u : 0u;
+    }
+    return COX_OK;
+  }();
+  (void)hipHostFree(pinned);
   return st;
 }
 

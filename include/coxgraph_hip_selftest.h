@@ -1,7 +1,11 @@
 /* Self-test entry points into the device-wide primitives of libcoxgraph_hip.so: the stable LSD radix sort and the three-launch
  * exclusive scan (coxgraph_amd/csrc/cox_sort.hpp), and the two one-workgroup scans of the ray-generation chain
- * (coxgraph_amd/csrc/cox_frontend.hpp); and, last, the depth integrator's candidate box.  Only the test suite calls them
- * (tests/test_gpu_sort_scan.py, tests/test_depthfuse_abi_cpu.py, tests/test_gpu_depthfuse.py); no product path does.
+ * (coxgraph_amd/csrc/cox_frontend.hpp); the input side of a frame, also of cox_frontend.hpp: the depth front end (k_depth_count,
+ * k_depth_points) and the kernel that reads pinned host inputs (k_copy_from_host); and, last, the depth integrator's candidate
+ * box.  Only the test suite calls them (tests/test_gpu_sort_scan.py, tests/test_gpu_frontend.py, tests/test_depthfuse_abi_cpu.py,
+ * tests/test_gpu_depthfuse.py); no product path does.  The two input-side entries follow the rules below as well: host arrays in
+ * and out, the null stream, COX_ERR_NO_DEVICE checked first, then COX_ERR_INVALID_ARG (a missing array, an empty image, a size
+ * above 2^24, a grid above 65535, groups outside 1..1024).
  *
  * Kept apart from coxgraph_hip.h on purpose: these symbols have no counterpart in the CPU checker.  Every sort or scan entry takes host arrays,
  * allocates what it needs on `device`, runs the primitive on the null stream exactly as the engine's call sites do, copies back
@@ -77,6 +81,23 @@ int cox_selftest_scan(int device, const uint32_t* in, uint32_t n_max, int use_d_
 int cox_selftest_scan_small(int device, const uint32_t* in_a, const uint32_t* in_b, uint32_t len, uint32_t n_max, uint32_t d_n,
                             uint32_t sentinel, uint32_t* out1_a, uint32_t* out1_b, uint32_t* out2_a, uint32_t* out2_b,
                             uint32_t totals[4]);
+
+/* The depth front end: k_depth_count, then k_depth_points, on the w x h image `depth` (row-major; rgba NULL: no colour image), launched
+ * by the code the integrator launches them with.  grid 0: the engine's grid, one workgroup per tile of 2048 pixels; any other grid
+ * (up to 65535) makes both kernels stride over the tiles.  xyz_out [3 w h], rgba_out [w h] words, tile_sums_out
+ * [max(1, ceil(w h / 2048))] and *n_out are pre-filled with `sentinel`; want_rgba == 0 hands the kernel no colour output, so rgba_out
+ * comes back as sentinels.  Every output array has a guard of 64 sentinel words behind it: guard_touched = the words of each that
+ * changed, in the order xyz, rgba, tile_sums.  w h is at most 2^24. */
+int cox_selftest_depth_points(int device, const float* depth, const uint8_t* rgba, int w, int h, const float K[4], uint32_t grid, int want_rgba,
+                              uint32_t sentinel, float* xyz_out, uint8_t* rgba_out, uint32_t* tile_sums_out, uint32_t* n_out,
+                              uint32_t guard_touched[3]);
+
+/* k_copy_from_host with `groups` workgroups (1..1024) on a [words_a] and b [words_b] (b NULL with words_b == 0: no second segment),
+ * both copied to pinned host memory first; the segments are built by the code the integrator builds them with.  The destinations
+ * are pre-filled with `sentinel` and come back in out_a [words_a], out_b [words_b]; guard_touched = the words that changed among the
+ * 64 behind each destination (the guard of b is there without b, too).  words_a, words_b at most 2^24. */
+int cox_selftest_copy_from_host(int device, const uint32_t* a, uint64_t words_a, const uint32_t* b, uint64_t words_b, int groups, uint32_t sentinel,
+                                uint32_t* out_a, uint32_t* out_b, uint32_t guard_touched[2]);
 
 /* The box of candidate blocks a frame of the depth integrator (coxgraph_hip_depthfuse.h, cox_depthfuse.hip) would visit, computed
  * on the host: the one entry here that needs no GPU and checks for none.  lo[3] is the box's lowest block index, dims[3] its extent
