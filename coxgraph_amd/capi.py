@@ -1506,6 +1506,22 @@ class StereoCalibration(C.Structure):
     _fields_ = [("cam", StereoCamera * 2), ("T_cn_cnm1", C.c_double * 16)]
 
 
+class StereoFilterConfig(C.Structure):
+    """cox_stereo_filter_config (include/coxgraph_hip_stereo_filter.h)."""
+    _fields_ = [("median_size", C.c_int32), ("speckle_window", C.c_int32), ("speckle_range16", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class StereoFilterStats(C.Structure):
+    """cox_stereo_filter_stats."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_median_changed", "n_components", "n_speckle_components", "n_speckle_pixels")] + \
+               [(n, C.c_double) for n in ("median_ms", "speckle_ms")]
+
+    def asdict(self):
+        return {n: (float(getattr(self, n)) if t is C.c_double else int(getattr(self, n))) for n, t in self._fields_}
+
+
+STEREO_FILTER_BUFFERS = {"disparity_raw": 0, "disparity_median": 1, "labels": 2}  # cox_stereo_filter_buffer
+
 CAMERA_MODELS = {"pinhole": 0, "omni": 1, "eucm": 2, "ds": 3}
 DISTORTION_MODELS = {"radtan": 0, "equidistant": 1, "fov": 2, "none": 3}
 
@@ -1620,6 +1636,34 @@ class StereoMatcher(_Handle):
                      3: ((self.h, self.w), np.uint16)}[k]
         out = np.empty(shape, dt)
         self._call("stereo_download", C.c_int(k), _fp(out), C.c_uint64(out.nbytes))
+        return out
+
+    # the filters on the disparity (include/coxgraph_hip_stereo_filter.h); both are off at first
+    def set_filters(self, median_size=0, speckle_window=0, speckle_range16=16):
+        """cox_stereo_set_filters: a 3 x 3 median (median_size 3) and a speckle filter (components of at most speckle_window pixels,
+        linked by differences of at most speckle_range16 sixteenths of a pixel); holds from the next frame"""
+        c = StereoFilterConfig(int(median_size), int(speckle_window), int(speckle_range16), 0)
+        self._call("stereo_set_filters", C.byref(c))
+
+    @property
+    def filters(self):
+        """the setting as a StereoFilterConfig"""
+        c = StereoFilterConfig()
+        self._call("stereo_get_filters", C.byref(c))
+        return c
+
+    def filter_stats(self):
+        """cox_stereo_filter_last_stats as a dict; zeros when the last frame ran unfiltered"""
+        st = StereoFilterStats()
+        self._call("stereo_filter_last_stats", C.byref(st))
+        return st.asdict()
+
+    def filter_download(self, which):
+        """a filter stage of the last frame: "disparity_raw" (before 7a) / "disparity_median" (after 7a) uint16 [h, w], "labels"
+        uint32 [h, w] (0xFFFFFFFF: invalid)"""
+        k = STEREO_FILTER_BUFFERS[which] if isinstance(which, str) else int(which)
+        out = np.empty((self.h, self.w), np.uint32 if k == 2 else np.uint16)
+        self._call("stereo_filter_download", C.c_int(k), _fp(out), C.c_uint64(out.nbytes))
         return out
 
 

@@ -11,6 +11,7 @@
 #include "../../include/coxgraph_hip_selftest.h"
 #include "cox_host.hpp"
 #include "cox_sort.hpp"
+#include "cox_stereo_filter.hpp"
 
 using namespace cox;
 
@@ -225,5 +226,56 @@ int cox_selftest_scan(int device, const uint32_t* in, uint32_t n_max, int use_d_
   COX_HIP(hipDeviceSynchronize());
   COX_TRY(download(out, d_result, n_max));
   COX_TRY(download(total, d_total.p, 1));
+  return COX_OK;
+}
+
+// Steps 7a and 7b of dense stereo on a caller's disparity image, through the two launch functions of cox_stereo_filter.hpp that
+// cox_stereo.hip uses.  One allocation of words: the input, then every output with its guard behind it, the sizes, the counters.
+int cox_selftest_stereo_filters(int device, const uint16_t* disparity, int w, int h, const cox_stereo_filter_config* cfg, uint16_t* median_out,
+                                uint32_t* labels_out, uint16_t* filtered_out, uint64_t counts[4], uint32_t guard_touched[3]) {
+  COX_ENTRY();
+  COX_TRY(select_device(device));
+  if (!disparity || !median_out || !labels_out || !filtered_out || !counts || !guard_touched) return COX_ERR_INVALID_ARG;
+  if (w < 1 || h < 1 || w > COX_STEREO_MAX_SIDE || h > COX_STEREO_MAX_SIDE || static_cast<u64>(w) * static_cast<u64>(h) > (1ull << 24))
+    return COX_ERR_INVALID_ARG;
+  cox_stereo_filter_config c{0, 0, 16, 0};
+  if (cfg) c = *cfg;
+  if (!cox_stf::stf_config_ok(c.median_size, c.speckle_window, c.speckle_range16, c.reserved)) return COX_ERR_INVALID_ARG;
+  constexpr size_t G = 64;
+  constexpr int kFill = 0xA5;
+  const size_t n = static_cast<size_t>(w) * h, half = (n + 1) / 2;
+  const size_t o_med = half, o_lab = o_med + half + G, o_filt = o_lab + n + G, o_size = o_filt + half + G, o_cnt = o_size + n;
+  const size_t words = o_cnt + cox_stf::kCntWords;
+  DevWords buf;
+  COX_TRY(buf.alloc(words));
+  u32* d = buf.p;
+  COX_HIP(hipMemset(d, kFill, words * sizeof(u32)));
+  COX_HIP(hipMemset(d + o_cnt, 0, cox_stf::kCntWords * sizeof(u32)));
+  COX_HIP(hipMemcpy(d, disparity, n * sizeof(uint16_t), hipMemcpyHostToDevice));
+  COX_HIP(hipDeviceSynchronize());
+  const bool median = c.median_size == 3, speckle = c.speckle_window > 0;
+  const uint16_t* image = reinterpret_cast<const uint16_t*>(d);
+  uint16_t* d_med = reinterpret_cast<uint16_t*>(d + o_med);
+  uint16_t* d_filt = reinterpret_cast<uint16_t*>(d + o_filt);
+  if (median) {
+    cox_stf::stf_launch_median(image, w, h, d_med, nullptr, d + o_cnt, nullptr);
+    image = d_med;
+  }
+  if (speckle) cox_stf::stf_launch_speckle(image, w, h, c.speckle_window, c.speckle_range16, d + o_lab, d + o_size, d_filt, nullptr, d + o_cnt, nullptr);
+  COX_HIP(hipGetLastError());
+  COX_HIP(hipDeviceSynchronize());
+  COX_HIP(hipMemcpy(median_out, image, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  COX_HIP(hipMemcpy(labels_out, d + o_lab, n * sizeof(u32), hipMemcpyDeviceToHost));
+  COX_HIP(hipMemcpy(filtered_out, speckle ? d_filt : image, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  u32 h_counts[cox_stf::kCntWords];
+  COX_TRY(download(h_counts, d + o_cnt, cox_stf::kCntWords));
+  for (int k = 0; k < cox_stf::kCntWords; ++k) counts[k] = h_counts[k];
+  // a guard runs from the last element of its array to the next array: the half word behind an odd image counts as guard
+  const size_t first[3] = {o_med * 4 + n * 2, (o_lab + n) * 4, o_filt * 4 + n * 2}, stop[3] = {o_lab * 4, o_filt * 4, o_size * 4};
+  for (int k = 0; k < 3; ++k) {
+    std::vector<uint8_t> g(stop[k] - first[k]);
+    COX_HIP(hipMemcpy(g.data(), reinterpret_cast<const uint8_t*>(d) + first[k], g.size(), hipMemcpyDeviceToHost));
+    guard_touched[k] = static_cast<u32>(std::count_if(g.begin(), g.end(), [](uint8_t b) { return b != kFill; }));
+  }
   return COX_OK;
 }

@@ -13,6 +13,12 @@
 //   k_st_right         dR of step 6: one wave per right pixel
 //   k_st_depth         steps 6 and 8, the disparity image, rgba and the counts
 //
+// With a filter switched on (include/coxgraph_hip_stereo_filter.h; both are off until cox_stereo_set_filters) the tail of the chain is
+//   k_st_depth<false>  step 6 alone: the disparity before the filters, rgba, the two rejection counts
+//   stf_launch_median  step 7a and stf_launch_speckle step 7b, of cox_stereo_filter.hpp, whichever is on
+//   k_st_step8         step 8 on the filtered disparity: depth and its two counts
+// still one stream, a fixed chain, no allocation and no host read.  With both off the chain above is untouched.
+//
 // Every loop is bounded by a launch-time constant (the length of a line, K); no kernel waits for another workgroup; a wave of
 // a path kernel never diverges: the line, its length and every branch on them are wave-uniform, lanes differ in data only.
 // Every index is formed in size_t from values checked at create: w, h <= 2^15 and w * h * D <= 2^31.
@@ -22,8 +28,9 @@
 #include <cstring>
 #include <new>
 
-#include "../../include/coxgraph_hip_stereo.h"
+#include "../../include/coxgraph_hip_stereo_filter.h"
 #include "cox_host.hpp"
+#include "cox_stereo_filter.hpp"
 
 namespace {
 
@@ -301,6 +308,8 @@ __global__ void __launch_bounds__(kThreads) k_st_right(const u16* __restrict__ S
 }
 
 // ---- steps 6 and 8 -----------------------------------------------------------------------------------------------------------------
+// STEP8 false: step 6 alone, for a frame whose disparity goes through the filters first (depth is not touched, nor its two counts)
+template <bool STEP8>
 __global__ void __launch_bounds__(kThreads) k_st_depth(const u32* __restrict__ win, const u16* __restrict__ d_right, const ull* __restrict__ cl,
                                                        const u8* __restrict__ mask, const u8* __restrict__ rect_left, int w, u32 n_px, int lr_max_diff,
                                                        float fB16, float min_depth, float max_depth, float* __restrict__ depth,
@@ -324,17 +333,19 @@ __global__ void __launch_bounds__(kThreads) k_st_depth(const u32* __restrict__ w
       rej_lr = x - d0 < 0 || abs(static_cast<int>(d_right[pix - d0]) - d0) > lr_max_diff;
     }
     const bool valid = usable && !rej_unique && !rej_lr && d16 > 0;
-    float z = __builtin_nanf("");
-    if (valid) {
-      const float zz = fB16 / static_cast<float>(d16);
-      if (zz < min_depth || zz > max_depth)
-        ++n_depth;
-      else
-        z = zz, ++n_valid;
+    if (STEP8) {
+      float z = __builtin_nanf("");
+      if (valid) {
+        const float zz = fB16 / static_cast<float>(d16);
+        if (zz < min_depth || zz > max_depth)
+          ++n_depth;
+        else
+          z = zz, ++n_valid;
+      }
+      depth[pix] = z;
     }
     n_unique += usable && rej_unique;
     n_lr += usable && !rej_unique && rej_lr;
-    depth[pix] = z;
     const u16 dv = valid ? static_cast<u16>(d16) : static_cast<u16>(0xffff);
     disparity[pix] = dv;
     if (disparity_user_or_null) disparity_user_or_null[pix] = dv;
@@ -350,6 +361,34 @@ __global__ void __launch_bounds__(kThreads) k_st_depth(const u32* __restrict__ w
   if (n_depth) atomicAdd(&block_counts[kCntDepth], n_depth);
   __syncthreads();
   if (threadIdx.x < kCntWords && block_counts[threadIdx.x]) atomicAdd(&counters[threadIdx.x], block_counts[threadIdx.x]);
+}
+
+// step 8 alone, on the disparity image the filters left
+__global__ void __launch_bounds__(kThreads) k_st_step8(const u16* __restrict__ disparity, u32 n_px, float fB16, float min_depth, float max_depth,
+                                                       float* __restrict__ depth, u32* __restrict__ counters) {
+  __shared__ u32 block_counts[2];
+  if (threadIdx.x < 2) block_counts[threadIdx.x] = 0;
+  __syncthreads();
+  u32 n_valid = 0, n_depth = 0;
+  for (int j = 0; j < kDepthPixelsPerThread; ++j) {
+    const size_t pix = (static_cast<size_t>(blockIdx.x) * kDepthPixelsPerThread + j) * kThreads + threadIdx.x;
+    if (pix >= n_px) break;
+    const int d16 = disparity[pix];
+    float z = __builtin_nanf("");
+    if (d16 != 0xffff) {
+      const float zz = fB16 / static_cast<float>(d16);
+      if (zz < min_depth || zz > max_depth)
+        ++n_depth;
+      else
+        z = zz, ++n_valid;
+    }
+    depth[pix] = z;
+  }
+  if (n_valid) atomicAdd(&block_counts[0], n_valid);
+  if (n_depth) atomicAdd(&block_counts[1], n_depth);
+  __syncthreads();
+  if (threadIdx.x == 0 && block_counts[0]) atomicAdd(&counters[kCntValid], block_counts[0]);
+  if (threadIdx.x == 1 && block_counts[1]) atomicAdd(&counters[kCntDepth], block_counts[1]);
 }
 
 // ---- step R (host) -----------------------------------------------------------------------------------------------------------------
@@ -392,6 +431,10 @@ bool config_ok(const cox_stereo_config& c) {
   return c.reserved == 0;
 }
 
+bool filter_config_ok(const cox_stereo_filter_config& c) {
+  return cox_stf::stf_config_ok(c.median_size, c.speckle_window, c.speckle_range16, c.reserved);
+}
+
 }  // namespace
 
 struct cox_stereo {
@@ -412,6 +455,15 @@ struct cox_stereo {
   float* d_depth = nullptr;  // outputs of cox_stereo_compute before they go to the host
   u8* d_rgba = nullptr;
   u32* h_counters = nullptr;  // pinned
+  // the filters on the disparity (coxgraph_hip_stereo_filter.h): nothing below exists until one is switched on
+  cox_stereo_filter_config fcfg{0, 0, 16, 0};
+  bool filter_bufs = false;
+  bool last_filtered = false, last_labelled = false;  // of the last frame
+  const u16* last_median = nullptr;                   // where the last frame left the image after 7a
+  u16 *f_raw = nullptr, *f_median = nullptr;
+  u32 *f_parent = nullptr, *f_size = nullptr, *f_counters = nullptr;
+  u32* h_fcounters = nullptr;  // pinned
+  hipEvent_t ev_f[3] = {};     // behind step 6, behind 7a, behind 7b
 };
 
 namespace {
@@ -420,10 +472,14 @@ size_t n_px_of(const cox_stereo* H) { return static_cast<size_t>(H->w) * H->h; }
 
 void release(cox_stereo* H) {
   void* bufs[] = {H->d_map0,        H->d_map1,         H->d_in_left, H->d_in_right, H->d_rect_left, H->d_rect_right, H->d_mask,  H->d_census_left,
-                  H->d_census_right, H->d_S,           H->d_right,   H->d_disparity, H->d_win,      H->d_counters,   H->d_depth, H->d_rgba};
+                  H->d_census_right, H->d_S,           H->d_right,   H->d_disparity, H->d_win,      H->d_counters,   H->d_depth, H->d_rgba,
+                  H->f_raw,          H->f_median,      H->f_parent,  H->f_size,      H->f_counters};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   if (H->h_counters) (void)hipHostFree(H->h_counters);
+  if (H->h_fcounters) (void)hipHostFree(H->h_fcounters);
+  for (hipEvent_t e : H->ev_f)
+    if (e) (void)hipEventDestroy(e);
   if (H->ev_in) (void)hipEventDestroy(H->ev_in);
   if (H->ev_read) (void)hipEventDestroy(H->ev_read);
   for (hipEvent_t e : H->ev_t)
@@ -476,9 +532,35 @@ int enqueue_frame(cox_stereo* H, const u8* left, const u8* right, float* depth, 
     default: COX_TRY(launch_paths_and_winner<4>(H)); break;
   }
   const u32 depth_groups = (n_px + kThreads * kDepthPixelsPerThread - 1) / (kThreads * kDepthPixelsPerThread);
-  k_st_depth<<<depth_groups, kThreads, 0, s>>>(H->d_win, H->d_right, H->d_census_left, H->d_mask, H->d_rect_left, w, n_px, H->cfg.lr_max_diff, H->fB16,
-                                            H->cfg.min_depth_m, H->cfg.max_depth_m, depth, rgba_or_null, H->d_disparity, disparity_or_null, H->d_counters);
+  const bool median = H->fcfg.median_size == 3, speckle = H->fcfg.speckle_window > 0;
+  if (!median && !speckle) {
+    k_st_depth<true><<<depth_groups, kThreads, 0, s>>>(H->d_win, H->d_right, H->d_census_left, H->d_mask, H->d_rect_left, w, n_px, H->cfg.lr_max_diff,
+                                                    H->fB16, H->cfg.min_depth_m, H->cfg.max_depth_m, depth, rgba_or_null, H->d_disparity,
+                                                    disparity_or_null, H->d_counters);
+  } else {
+    // steps 6, 7a, 7b, 8: the last stage that is on writes the final image, for cox_stereo_download and for the caller
+    COX_HIP(hipMemsetAsync(H->f_counters, 0, sizeof(u32) * cox_stf::kCntWords, s));
+    k_st_depth<false><<<depth_groups, kThreads, 0, s>>>(H->d_win, H->d_right, H->d_census_left, H->d_mask, H->d_rect_left, w, n_px, H->cfg.lr_max_diff,
+                                                     H->fB16, H->cfg.min_depth_m, H->cfg.max_depth_m, nullptr, rgba_or_null, H->f_raw, nullptr,
+                                                     H->d_counters);
+    COX_HIP(hipEventRecord(H->ev_f[0], s));
+    const u16* image = H->f_raw;
+    if (median) {
+      u16* out = speckle ? H->f_median : H->d_disparity;
+      cox_stf::stf_launch_median(image, w, h, out, speckle ? nullptr : disparity_or_null, H->f_counters, s);
+      image = out;
+    }
+    H->last_median = image;
+    COX_HIP(hipEventRecord(H->ev_f[1], s));
+    if (speckle)
+      cox_stf::stf_launch_speckle(image, w, h, H->fcfg.speckle_window, H->fcfg.speckle_range16, H->f_parent, H->f_size, H->d_disparity, disparity_or_null,
+                                  H->f_counters, s);
+    COX_HIP(hipEventRecord(H->ev_f[2], s));
+    k_st_step8<<<depth_groups, kThreads, 0, s>>>(H->d_disparity, n_px, H->fB16, H->cfg.min_depth_m, H->cfg.max_depth_m, depth, H->d_counters);
+  }
   COX_HIP(hipGetLastError());
+  H->last_filtered = median || speckle;
+  H->last_labelled = speckle;
   H->have_frame = true;
   return COX_OK;
 }
@@ -706,6 +788,11 @@ int cox_stereo_last_stats(cox_stereo_t* H, cox_stereo_stats* out) {
     for (int k = 0; k < kStages; ++k)
       if (hipEventElapsedTime(&t, H->ev_t[k], H->ev_t[k + 1]) == hipSuccess) *stage[k] = t;
     if (hipEventElapsedTime(&t, H->ev_t[0], H->ev_t[kStages]) == hipSuccess) out->frame_ms = t;
+    if (H->last_filtered) {  // steps 6 and 8 lie on either side of the filters
+      float t6 = 0.0f, t8 = 0.0f;
+      if (hipEventElapsedTime(&t6, H->ev_t[kStages - 1], H->ev_f[0]) == hipSuccess && hipEventElapsedTime(&t8, H->ev_f[2], H->ev_t[kStages]) == hipSuccess)
+        out->depth_ms = static_cast<double>(t6) + static_cast<double>(t8);
+    }
     (void)hipGetLastError();
   }
   return COX_OK;
@@ -723,6 +810,102 @@ int cox_stereo_download(cox_stereo_t* H, int which, void* buf, uint64_t cap_byte
     case COX_STEREO_RECT_RIGHT: src = H->d_rect_right, bytes = n_px; break;
     case COX_STEREO_COST_SUM: src = H->d_S, bytes = sizeof(u16) * n_px * static_cast<size_t>(H->cfg.n_disparities); break;
     case COX_STEREO_DISPARITY: src = H->d_disparity, bytes = sizeof(u16) * n_px; break;
+    default: return COX_ERR_INVALID_ARG;
+  }
+  if (cap_bytes < bytes) return COX_ERR_BUFFER_TOO_SMALL;
+  COX_HIP(hipSetDevice(H->device));
+  COX_HIP(hipMemcpyAsync(buf, src, bytes, hipMemcpyDeviceToHost, H->stream));
+  COX_HIP(hipStreamSynchronize(H->stream));
+  return COX_OK;
+}
+
+// ---- the filters on the disparity (coxgraph_hip_stereo_filter.h) ------------------------------------------------------------------
+void cox_stereo_filter_config_default(cox_stereo_filter_config* cfg) {
+  if (!cfg) return;
+  cfg->median_size = 0;
+  cfg->speckle_window = 0;
+  cfg->speckle_range16 = 16;
+  cfg->reserved = 0;
+}
+
+int cox_stereo_set_filters(cox_stereo_t* H, const cox_stereo_filter_config* cfg) {
+  COX_ENTRY_NO_DRAIN();
+  COX_TRY(device_present());
+  if (!H) return COX_ERR_INVALID_ARG;
+  cox_stereo_filter_config c;
+  cox_stereo_filter_config_default(&c);
+  if (cfg) c = *cfg;
+  if (!filter_config_ok(c)) return COX_ERR_INVALID_ARG;
+  COX_HIP(hipSetDevice(H->device));
+  COX_HIP(hipStreamSynchronize(H->stream));
+  if ((c.median_size != 0 || c.speckle_window > 0) && !H->filter_bufs) {
+    const size_t n_px = n_px_of(H);
+    bool ok = true;
+    for (hipEvent_t& e : H->ev_f) ok = ok && (e != nullptr || hipEventCreate(&e) == hipSuccess);
+    auto dev_alloc = [&ok](auto** p, size_t bytes) { ok = ok && (*p != nullptr || hipMalloc(reinterpret_cast<void**>(p), bytes) == hipSuccess); };
+    dev_alloc(&H->f_raw, sizeof(u16) * n_px);
+    dev_alloc(&H->f_median, sizeof(u16) * n_px);
+    dev_alloc(&H->f_parent, sizeof(u32) * n_px);
+    dev_alloc(&H->f_size, sizeof(u32) * n_px);
+    dev_alloc(&H->f_counters, sizeof(u32) * cox_stf::kCntWords);
+    ok = ok && (H->h_fcounters != nullptr ||
+                hipHostMalloc(reinterpret_cast<void**>(&H->h_fcounters), sizeof(u32) * cox_stf::kCntWords, hipHostMallocDefault) == hipSuccess);
+    if (!ok) {  // what was allocated stays with the handle for the next attempt; the setting does not change
+      (void)hipGetLastError();
+      return COX_ERR_OUT_OF_MEMORY;
+    }
+    H->filter_bufs = true;
+  }
+  H->fcfg = c;
+  return COX_OK;
+}
+
+int cox_stereo_get_filters(cox_stereo_t* H, cox_stereo_filter_config* out) {
+  COX_ENTRY_NO_DRAIN();
+  COX_TRY(device_present());
+  if (!H || !out) return COX_ERR_INVALID_ARG;
+  *out = H->fcfg;
+  return COX_OK;
+}
+
+int cox_stereo_filter_last_stats(cox_stereo_t* H, cox_stereo_filter_stats* out) {
+  COX_ENTRY_NO_DRAIN();
+  COX_TRY(device_present());
+  if (!H || !out) return COX_ERR_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!H->have_frame) return COX_OK;
+  COX_HIP(hipSetDevice(H->device));
+  if (!H->last_filtered) {
+    COX_HIP(hipStreamSynchronize(H->stream));
+    return COX_OK;
+  }
+  COX_HIP(hipMemcpyAsync(H->h_fcounters, H->f_counters, sizeof(u32) * cox_stf::kCntWords, hipMemcpyDeviceToHost, H->stream));
+  COX_HIP(hipStreamSynchronize(H->stream));
+  out->n_median_changed = H->h_fcounters[cox_stf::kCntMedianChanged];
+  out->n_components = H->h_fcounters[cox_stf::kCntComponents];
+  out->n_speckle_components = H->h_fcounters[cox_stf::kCntSpeckleComponents];
+  out->n_speckle_pixels = H->h_fcounters[cox_stf::kCntSpecklePixels];
+  float t = 0.0f;
+  if (hipEventElapsedTime(&t, H->ev_f[0], H->ev_f[1]) == hipSuccess) out->median_ms = t;
+  if (hipEventElapsedTime(&t, H->ev_f[1], H->ev_f[2]) == hipSuccess) out->speckle_ms = t;
+  (void)hipGetLastError();
+  return COX_OK;
+}
+
+int cox_stereo_filter_download(cox_stereo_t* H, int which, void* buf, uint64_t cap_bytes) {
+  COX_ENTRY_NO_DRAIN();
+  COX_TRY(device_present());
+  if (!H || !buf || !H->have_frame || !H->last_filtered) return COX_ERR_INVALID_ARG;
+  const size_t n_px = n_px_of(H);
+  const void* src = nullptr;
+  size_t bytes = 0;
+  switch (which) {
+    case COX_STEREO_FILTER_DISPARITY_RAW: src = H->f_raw, bytes = sizeof(u16) * n_px; break;
+    case COX_STEREO_FILTER_DISPARITY_MEDIAN: src = H->last_median, bytes = sizeof(u16) * n_px; break;
+    case COX_STEREO_FILTER_LABELS:
+      if (!H->last_labelled) return COX_ERR_INVALID_ARG;
+      src = H->f_parent, bytes = sizeof(u32) * n_px;
+      break;
     default: return COX_ERR_INVALID_ARG;
   }
   if (cap_bytes < bytes) return COX_ERR_BUFFER_TOO_SMALL;

@@ -5,7 +5,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "../../include/coxgraph_hip_stereo.h"
+#include "../../include/coxgraph_hip_stereo_filter.h"
 #include "coxgraph_hip_adapters.hpp"
 
 namespace coxgraph_hip {
@@ -59,6 +59,9 @@ class DenseStereo {
   struct Config : cox_stereo_config {
     Config() { cox_stereo_config_default(this); }
   };
+  struct FilterConfig : cox_stereo_filter_config {
+    FilterConfig() { cox_stereo_filter_config_default(this); }
+  };
 
   // raw pairs, rectified with r's maps
   DenseStereo(const StereoRectification& r, const Config& config = Config(), int device = 0) : config_(config), width_(r.width), height_(r.height) {
@@ -102,6 +105,19 @@ class DenseStereo {
   cox_stereo_stats lastStats() {
     cox_stereo_stats st;
     check(cox_stereo_last_stats(h_, &st), "DenseStereo::lastStats");
+    return st;
+  }
+  // the median and the speckle filter on the disparity (steps 7a and 7b); both are off at first, and a setting holds from the next frame
+  void setFilters(const FilterConfig& filters) { check(cox_stereo_set_filters(h_, &filters), "DenseStereo::setFilters"); }
+  FilterConfig filters() const {
+    FilterConfig f;
+    check(cox_stereo_get_filters(h_, &f), "DenseStereo::filters");
+    return f;
+  }
+  // of the last frame; zeros when it ran unfiltered
+  cox_stereo_filter_stats filterStats() {
+    cox_stereo_filter_stats st;
+    check(cox_stereo_filter_last_stats(h_, &st), "DenseStereo::filterStats");
     return st;
   }
   // an intermediate of the last frame (a cox_stereo_buffer), as bytes

@@ -1,9 +1,10 @@
 /* Self-test entry points into the device-wide primitives of libcoxgraph_hip.so: the stable LSD radix sort and the three-launch
  * exclusive scan (coxgraph_amd/csrc/cox_sort.hpp), and the two one-workgroup scans of the ray-generation chain
  * (coxgraph_amd/csrc/cox_frontend.hpp); the input side of a frame, also of cox_frontend.hpp: the depth front end (k_depth_count,
- * k_depth_points) and the kernel that reads pinned host inputs (k_copy_from_host); and, last, the depth integrator's candidate
- * box.  Only the test suite calls them (tests/test_gpu_sort_scan.py, tests/test_gpu_frontend.py, tests/test_depthfuse_abi_cpu.py,
- * tests/test_gpu_depthfuse.py); no product path does.  The two input-side entries follow the rules below as well: host arrays in
+ * k_depth_points) and the kernel that reads pinned host inputs (k_copy_from_host); the depth integrator's candidate
+ * box; and, last, the two filters on the disparity of dense stereo (coxgraph_amd/csrc/cox_stereo_filter.hpp).  Only the test suite
+ * calls them (tests/test_gpu_sort_scan.py, tests/test_gpu_frontend.py, tests/test_depthfuse_abi_cpu.py, tests/test_gpu_depthfuse.py,
+ * tests/test_gpu_stereo_filter.py); no product path does.  The two input-side entries follow the rules below as well: host arrays in
  * and out, the null stream, COX_ERR_NO_DEVICE checked first, then COX_ERR_INVALID_ARG (a missing array, an empty image, a size
  * above 2^24, a grid above 65535, groups outside 1..1024).
  *
@@ -16,6 +17,7 @@
 #define COXGRAPH_HIP_SELFTEST_H_
 #include "coxgraph_hip.h"
 #include "coxgraph_hip_depthfuse.h"
+#include "coxgraph_hip_stereo_filter.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -106,6 +108,18 @@ int cox_selftest_copy_from_host(int device, const uint32_t* a, uint64_t words_a,
  * (COX_ERR_INVALID_ARG, COX_ERR_INDEX_RANGE). */
 int cox_selftest_depthfuse_box(float voxel_size, const cox_depthfuse_config* cfg, const float T_G_C[7], int w, int height, const float K[4],
                                int32_t lo[3], uint32_t dims[3]);
+
+/* Steps 7a and 7b of dense stereo (coxgraph_hip_stereo_filter.h, coxgraph_amd/csrc/cox_stereo_filter.hpp) on a w x h disparity image
+ * the caller supplies (u16, 1/16 px, 0xFFFF invalid), launched by the two functions the matcher launches them with, on the null
+ * stream: whole frames cannot be made to produce the images that try a labelling.  cfg as cox_stereo_set_filters takes it (NULL:
+ * both off).  median_out [w h]: the image after 7a (the input when the median is off); labels_out [w h]: 7b's labels; filtered_out
+ * [w h]: the image after 7b; counts: n_median_changed, n_components, n_speckle_components, n_speckle_pixels.  With 7b off nothing
+ * is labelled: labels_out comes back as its pre-fill, filtered_out is the image after 7a and the last three counts are 0.  The
+ * outputs are pre-filled with 0xA5 bytes, with 64 guard words of the same behind each: guard_touched = the bytes of each guard that
+ * changed, in the order median, labels, filtered.  COX_ERR_INVALID_ARG: a missing array, w or h outside 1 .. 2^15, w h above 2^24,
+ * a configuration cox_stereo_set_filters refuses. */
+int cox_selftest_stereo_filters(int device, const uint16_t* disparity, int w, int h, const cox_stereo_filter_config* cfg, uint16_t* median_out,
+                                uint32_t* labels_out, uint16_t* filtered_out, uint64_t counts[4], uint32_t guard_touched[3]);
 
 #ifdef __cplusplus
 }

@@ -4,8 +4,9 @@
  * its output.  The depth image written here has the layout of the renderer, the tracker and cox_depthfuse_integrate_dev (w * h
  * floats, row-major, z-depth in metres, NaN where there is nothing, K = {fx, fy, cx, cy}), so pair -> depth -> fusion stays on
  * the device.  The rule of one frame (steps R and 1-8) is integer arithmetic from the census to the disparity and is stated in
- * DESIGN.md section 7n; tests/stereo_ref.py restates it in numpy and the kernels owe it every bit.  Not done: a speckle or median
- * filter, a minimum disparity other than 0, an adaptive P2, colour inputs, fisheye models, OpenCV StereoSGBM parity.
+ * DESIGN.md section 7n; tests/stereo_ref.py restates it in numpy and the kernels owe it every bit.  A median and a speckle filter
+ * on the disparity are switched on through coxgraph_hip_stereo_filter.h.  Not done: a minimum disparity other than 0, an adaptive
+ * P2, colour inputs, fisheye models, OpenCV StereoSGBM parity.
  *
  * Kept apart from coxgraph_hip.h on purpose, like coxgraph_hip_depthfuse.h: these entry points have no counterpart in the CPU
  * checker of the test suite.  Conventions are those of coxgraph_hip_map.h (COX_OK or a negative cox_status; where a device is
