@@ -90,11 +90,28 @@ __device__ __forceinline__ F3 normalized3(F3 a) {
   return a;
 }
 
+// The rare vertex the staged samples cannot serve: its block through the hash, one voxel (weight and colour word) from HBM.
+// l is clamped into the block by the caller; a block index beyond the packed keys names no block.
+__device__ __forceinline__ u32 vertex_color_unstaged(const MeshView& L, const int bb[3], const int l[3], float min_weight, bool* missing) {
+  u32 slot = kInvalid;
+  if (bb[0] >= -kIdxBias && bb[0] < kIdxBias && bb[1] >= -kIdxBias && bb[1] < kIdxBias && bb[2] >= -kIdxBias && bb[2] < kIdxBias)
+    slot = ht_find(L.ht_keys, L.ht_mask, pack_key(bb[0], bb[1], bb[2]));
+  if (slot == kInvalid) {
+    *missing = true;
+    return 0u;
+  }
+  const u32 lin = static_cast<u32>(l[0]) | (static_cast<u32>(l[1]) << 4) | (static_cast<u32>(l[2]) << 8);
+  const u32* vw = L.voxels + (static_cast<size_t>(L.ht_vals[slot]) * kVoxelsPerBlock + lin) * kWordsPerVoxel;
+  return __uint_as_float(vw[1]) > min_weight ? vw[2] : 0u;
+}
+
 // MeshIntegrator::updateMeshColor for one vertex: the voxel that contains it (computeVoxelIndexFromCoordinates); outside the
-// block, the block found by coordinates and the voxel clamped into it (getVoxelByCoordinates).  Both are always among the
-// staged 17^3 samples (the containing voxel is a corner of the vertex's cube); anything else is counted, never read.
+// block, the block found by coordinates and the voxel clamped into it (getVoxelByCoordinates); missing only when that block does
+// not exist.  Where a float coordinate resolves a voxel both are among the staged 17^3 samples (the containing voxel is a corner
+// of the vertex's cube).  Hundreds of thousands of blocks out it does not: the vertex can round into a block below its own or
+// into a voxel past the staged face, and vertex_color_unstaged serves it.
 __device__ __forceinline__ u32 vertex_color(const MeshView& L, F3 v, const int b[3], const float o[3], const u32* nbr_pool, const u32* col,
-                                            const unsigned char* ok, bool* missing) {
+                                            const unsigned char* ok, float min_weight, bool* missing) {
   const float p[3] = {v.x, v.y, v.z};
   int s[3];
   bool inside = true;
@@ -103,22 +120,22 @@ __device__ __forceinline__ u32 vertex_color(const MeshView& L, F3 v, const int b
     s[k] = grid_index((p[k] - o[k]) * L.voxel_size_inv);
     inside = inside && s[k] >= 0 && s[k] < kVps;
   }
-  u32 sel = 0;
   if (!inside) {
+    int bb[3], l[3];
+    u32 sel = 0;
+    bool staged = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      const int bb = grid_index(p[k] * L.block_size_inv);
-      const int d = bb - b[k];
-      const float ob = static_cast<float>(bb) * L.block_size;
-      int l = grid_index((p[k] - ob) * L.voxel_size_inv);
-      l = l < 0 ? 0 : (l > kVps - 1 ? kVps - 1 : l);
-      s[k] = d * kVps + l;
-      if (d < 0 || d > 1 || s[k] > kVps) {
-        *missing = true;
-        return 0u;
-      }
-      sel |= static_cast<u32>(d) << k;
+      bb[k] = grid_index(p[k] * L.block_size_inv);
+      const int d = bb[k] - b[k];
+      const float ob = static_cast<float>(bb[k]) * L.block_size;
+      l[k] = grid_index((p[k] - ob) * L.voxel_size_inv);
+      l[k] = l[k] < 0 ? 0 : (l[k] > kVps - 1 ? kVps - 1 : l[k]);
+      s[k] = d * kVps + l[k];
+      staged = staged && d >= 0 && d <= 1 && s[k] <= kVps;
+      sel |= (d == 1 ? 1u : 0u) << k;
     }
+    if (!staged) return vertex_color_unstaged(L, bb, l, min_weight, missing);
     if (nbr_pool[sel] == kInvalid) {
       *missing = true;
       return 0u;
@@ -234,7 +251,7 @@ __global__ void __launch_bounds__(256) k_mesh_block(MeshView L, const u32* __res
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         bool miss = false;
-        const u32 cw = vertex_color(L, v[j], b, o, nbr_pool, col, ok, &miss);
+        const u32 cw = vertex_color(L, v[j], b, o, nbr_pool, col, ok, min_weight, &miss);
         missing += miss ? 1u : 0u;
         pos[3 * vi] = v[j].x;
         pos[3 * vi + 1] = v[j].y;

@@ -267,10 +267,6 @@ def test_edge_cases(hip, submap):
     assert MeshLayer.from_layer(hip, layer, min_weight=1e9).n_triangles == 0
 
 
-def _c_round(x):
-    return np.sign(x) * np.floor(np.abs(x) + 0.5)
-
-
 def test_global_mesh_of_two_submaps_is_transform_plus_concatenation(hip, submap):
     voxel, layer = submap
     other, _, _ = run_frames(hip, method="merged", voxel=voxel, frames=range(70, 150, 10), subsample=4, capacity_blocks=8192)
@@ -285,16 +281,12 @@ def test_global_mesh_of_two_submaps_is_transform_plus_concatenation(hip, submap)
     for mm, t in zip(moved, T):
         mm.transform(t)
     cat = {k: np.concatenate([mm.download()[k] for mm in moved]) for k in ("xyz", "normals", "rgb")}
-    cells = _c_round(cat["xyz"].astype(np.float64) * (1.0 / np.float64(np.float32(thr)))).astype(np.int64)
-    _, first, inv = np.unique(cells, axis=0, return_index=True, return_inverse=True)
-    order = np.argsort(first)
-    rank = np.empty_like(order)
-    rank[order] = np.arange(len(order))
-    survivors = first[order]
+    weld = mesh_ref.weld_ref(cat["xyz"], cat["normals"], cat["rgb"], thr)
+    survivors = weld["survivors"]
     assert np.array_equal(_bits(got["xyz"]), _bits(cat["xyz"][survivors]))
     assert np.array_equal(_bits(got["normals"]), _bits(cat["normals"][survivors]))
     assert np.array_equal(got["rgb"], cat["rgb"][survivors])
-    assert np.array_equal(got["triangles"].reshape(-1), rank[inv.reshape(-1)])
+    assert np.array_equal(got["triangles"].reshape(-1), weld["triangles"].reshape(-1))
     # the rotation reached the normals: R n, still unit length where the triangle was not degenerate
     nn = np.linalg.norm(got["normals"], axis=1)
     assert np.all((np.abs(nn - 1) < 1e-5) | (nn == 0))
