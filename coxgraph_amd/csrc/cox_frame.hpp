@@ -70,6 +70,18 @@ struct RayArrays {
   u32* piece_off;           // exclusive scan of pbound
 };
 
+// the frame block table of the merged record walk (cox_walk.hpp, where it is explained)
+struct FrameBlocks {
+  u64* keys;   // [mask + 1] block key per slot; empty between frames (the binding empties the slots it reads)
+  u32* ord;    // [mask + 1] ordinal of the slot's key (valid while the key is there)
+  u32* slots;  // [mask + 1] the occupied slots in ordinal order: slots[0, n_touched)
+  u32 mask;
+};
+// per-axis crossing capacity of the parallel DDA (cox_walk.hpp: wave_ray_path) and the ray flags beyond bit 0 (valid) and bit 1 (clearing)
+constexpr u32 kAxisCapSmall = 128, kAxisCapLarge = 512;
+constexpr u32 kRayFallback = 4u;  // ray flag: the parallel walk does not cover this ray (sequential walk on lane 0, touch and emit alike)
+constexpr u32 kRayNoPath = 8u;    // ray flag: no path parked for emit (k_bundle_merge<true>: the ray's slot ends beyond the record buffers); emit walks it sequentially
+
 // both ping-pong buffers of the record sort + where the result ended up
 struct RecordView {
   const u32* key[2];

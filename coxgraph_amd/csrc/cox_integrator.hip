@@ -596,7 +596,8 @@ static int stage_point_sort(const StageCtx& c, hipStream_t s) {
 }
 // the merged record walk (RecordTiles, RecordsFullSort): few long rays, so one wave per ray (parallel DDA); the walk found by
 // k_touch_wave is handed to k_emit_wave through the spare sort buffer.  Both read the frame's rays and its own tables only
-// (cox_walk.hpp: FrameBlocks), so the plan may put them on the ray-generation stream (IntegratorPlan::walk_on_raygen).
+// (cox_walk.hpp: FrameBlocks), so the plan may put them on the ray-generation stream (IntegratorPlan::walk_on_raygen) -- and there,
+// with the small axis cap, the bundle merge does k_touch_wave's work itself (IntegratorPlan::touch_in_merge): emit is all that is left.
 static FrameBlocks frame_blocks(const cox_integrator* I, const RecordSet& S) { return FrameBlocks{S.ft_keys, S.ft_ord, S.touched_slots, I->layer->ht_cap - 1}; }
 static void record_walk(const StageCtx& c, hipStream_t s) {
   cox_integrator* I = c.I;
@@ -605,12 +606,14 @@ static void record_walk(const StageCtx& c, hipStream_t s) {
   RecordSet& S = *c.S;
   const u32 fh_mask = I->fh_cap - 1;
   const FrameBlocks FB = frame_blocks(I, S);
-  if (P.small_axis_cap)
+  if (P.touch_in_merge) {
+    // (done by stage_merge: the paths are parked in slots of steps_max words per ray)
+  } else if (P.small_axis_cap)
     hipLaunchKernelGGL(k_touch_wave<kAxisCapSmall>, dim3(P.grid_touch), dim3(256), 0, s, F.d_params, F.rays, FB, S.rec_key[1], I->rcap, F.cnt, F.fh_keys, fh_mask);
   else
     hipLaunchKernelGGL(k_touch_wave<kAxisCapLarge>, dim3(2048), dim3(256), 0, s, F.d_params, F.rays, FB, S.rec_key[1], I->rcap, F.cnt, F.fh_keys, fh_mask);
   hipLaunchKernelGGL(k_emit_wave, dim3(P.grid_touch), dim3(256), 0, s, F.d_params, F.rays, FB, S.rec_key[1], S.rec_key[0], S.rec_ray[0], I->rcap, F.cnt, S.sort_info,
-                     F.fh_keys, fh_mask, P.emit_flags());
+                     F.fh_keys, fh_mask, P.emit_flags(), P.touch_in_merge ? P.steps_max : 0u);
 }
 // one thread per block the frame touched (a few hundred at 5 cm, a few thousand at 2 cm); the grid strides.  Where the tile apply
 // follows (RecordTiles), the binding is done at the head of stage U by k_block_starts_bind instead: one launch less on the chain.
@@ -629,8 +632,15 @@ static int stage_merge(const StageCtx& c, hipStream_t s) {
     BundleView V{{B.skey[0], B.skey[1]}, {B.sval[0], B.sval[1]}, B.sort_info};
     {  // (the bundle boundaries were written by the sort's last pass)
       TimedRegion t(I, COX_KC_MERGE, s);
-      hipLaunchKernelGGL(k_bundle_merge, dim3(I->plan.grid_merge), dim3(256), 0, s, F.d_params, V, B.bstart, F.rays, F.cnt,
-                         I->plan.walks_pieces() ? (I->plan.small_axis_cap ? kAxisCapSmall : kAxisCapLarge) : 0u);  // (pieces: the rays' piece bounds)
+      if (I->plan.touch_in_merge) {  // the merge walks every ray it produces: it writes the record set's frame block table and path buffer
+        const RecordSet& S = *c.S;
+        const MergeWalk walk{frame_blocks(I, S), S.rec_key[1], I->plan.steps_max, I->rcap, F.fh_keys, I->fh_cap - 1};
+        hipLaunchKernelGGL(k_bundle_merge<true>, dim3(I->plan.grid_merge), dim3(256), 0, s, F.d_params, V, B.bstart, F.rays, F.cnt, 0u, walk);
+      } else {
+        hipLaunchKernelGGL(k_bundle_merge<false>, dim3(I->plan.grid_merge), dim3(256), 0, s, F.d_params, V, B.bstart, F.rays, F.cnt,
+                           I->plan.walks_pieces() ? (I->plan.small_axis_cap ? kAxisCapSmall : kAxisCapLarge) : 0u,  // (pieces: the rays' piece bounds)
+                           MergeWalk{});
+      }
     }
     // record offsets (and piece slots) of the rays: scanned here, on the ray-generation stream -- two frames' worth of it run
     // side by side, the layer-update chain is the one that bounds the frame rate
@@ -1124,6 +1134,10 @@ static int integrate_device(cox_integrator* I, const float T[7], const float* xy
   COX_TRY(chain(ctx, 0));
   COX_HIP(hipEventRecord(F.params_copied, s_h));
   COX_TRY(chain(ctx, 1));
+  // Where the merge does the walk (touch_in_merge) it writes the frame's record set -- the frame block table and the parked paths -- so
+  // the wait for the apply of the frame that used the set last, t-3, stands in front of stage M instead of in front of the walk (below;
+  // the same reasoning makes S.done and S.used safe to read here).  B.done and the inputs-read events are then recorded behind that wait.
+  if (I->plan.touch_in_merge && S.used) COX_HIP(hipStreamWaitEvent(s_m, S.done, 0));
   COX_TRY(chain(ctx, 2));
   COX_HIP(hipEventRecord(B.done, s_m));
   B.used = true;
@@ -1138,9 +1152,9 @@ static int integrate_device(cox_integrator* I, const float T[7], const float* xy
   // above) -- so S.done is recorded and S.used is there to read.  Three record sets: the lanes run at most three frames ahead of
   // the update.
   if (I->plan.walk_on_raygen) {
-    if (S.used) COX_HIP(hipStreamWaitEvent(s_m, S.done, 0));
+    if (S.used && !I->plan.touch_in_merge) COX_HIP(hipStreamWaitEvent(s_m, S.done, 0));
     {
-      TimedRegion t_walk(I, COX_KC_TOUCH_EMIT, s_m);
+      TimedRegion t_walk(I, COX_KC_TOUCH_EMIT, s_m);  // (touch_in_merge: emit alone; the touch is in the merge's class)
       record_walk(ctx, s_m);
     }
     if (stage_stream(I, 3, slot) != s_m) COX_HIP(hipEventRecord(F.hand[2], s_m));  // stage T waits for the walk, not only for the merge

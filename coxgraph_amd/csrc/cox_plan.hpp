@@ -19,7 +19,7 @@ namespace cox_plan {
 #define COX_PLAN_SWITCHES(X)                                                                                                                   \
   X(APPLY) X(APPLY_WAVE) X(BIG_CHUNK) X(BUCKETS) X(COPY_THREADS) X(DEBUG) X(DEPTH_CONVERT) X(FAST_CAP) X(FAST_FENCE) X(FAST_GROUPS)             \
   X(FAST_ROUNDS) X(FAST_SEQUENTIAL) X(FAST_STREAMS) X(GRAPH) X(GRID_APPLY) X(GRID_APPLY_WAVE) X(GRID_MERGE) X(GRID_TOUCH) X(H2D) X(H2D_GROUPS) \
-  X(INPUT_STREAM) X(NO_GRAPH) X(PARTITION) X(QUEUES) X(RECORD_CAP) X(SPLIT_TILES) X(STREAMS) X(STREAM_MAP) X(SUBMIT_THREAD) X(TILE) X(TIMELINE) X(WALK)       \
+  X(INPUT_STREAM) X(NO_GRAPH) X(PARTITION) X(QUEUES) X(RECORD_CAP) X(SPLIT_TILES) X(STREAMS) X(STREAM_MAP) X(SUBMIT_THREAD) X(TILE) X(TIMELINE) X(TOUCH) X(WALK) \
   X(WAVE_TILE_MAX)
 #define COX_PLAN_ENUM(n) k##n,
 #define COX_PLAN_NAME(n) "COX_" #n,
@@ -74,6 +74,8 @@ struct IntegratorPlan {
   int n_streams = 0;               // distinct streams in all
   bool walk_on_raygen = false;     // merged record walk (k_touch_wave, k_emit_wave) at the tail of stage M, on the frame's ray-generation stream;
                                    // stage T is then the binding of the frame's blocks to the layer alone
+  bool touch_in_merge = false;     // walk_on_raygen with the small axis cap: the walk of a ray (k_touch_wave's work) is done by the bundle merge, on the wave
+                                   // that has just produced the ray, and parked in a slot of steps_max words per ray; k_touch_wave is not launched
   // ---- host side
   bool use_graphs = false;     // stages replayed as captured HIP graphs
   bool submit_thread = true;   // stages T, R, U enqueued by a thread of the integrator's own
@@ -243,6 +245,12 @@ IntegratorPlan resolve_plan(int method, const cox_tsdf_config& cfg, float voxel_
     const bool can = merged && !p.walks_pieces() && !p.use_graphs;
     const bool rule = p.alt_raygen_stream && p.stage_stream[3] == p.stage_stream[5];
     p.walk_on_raygen = can && (is(kWALK, "raygen") ? true : is(kWALK, "update") ? false : rule);
+    // The lanes are what bounds the frame there, launches and gaps included, and the merge leaves the chip empty for most of its time
+    // (a handful of waves finish the largest bundles): the walk of every other ray runs under that tail, one launch fewer per frame
+    // (DESIGN.md section 6, round 8).  Small axis cap only: the walk's LDS scratch has to fit the merge's operand table.
+    // COX_TOUCH=merge|kernel replaces the rule where the walk is on the lanes with the small axis cap, and changes nothing elsewhere.
+    const bool may_touch_in_merge = p.walk_on_raygen && p.small_axis_cap;
+    p.touch_in_merge = may_touch_in_merge && !is(kTOUCH, "kernel");
   }
 
   // ---- fast.  At 5 cm two rounds settle every frame of the benchmark stream; at 2 cm and 1 cm nine frames in ten have a ray that

@@ -342,8 +342,27 @@ __device__ __forceinline__ u32 piece_bound(const Dda& d, u32 axis_cap) {
   return min(b, ns);
 }
 
+// the walk of one ray on its wave (cox_walk.hpp, which follows this file): what k_touch_wave does per ray
+template <u32 kAxisCap>
+__device__ void wave_touch_ray(const FrameParams& P, const RayArrays& R, const FrameBlocks& B, u32 r, u32 ns, u32 flags, Dda d, u64 own_key, float* tl, u32* path,
+                               u32 lane, u32* __restrict__ park, Counters* cnt, const u64* __restrict__ fh_keys, u32 fh_mask);
+
+// The walk placed in the merge (IntegratorPlan::touch_in_merge; small axis cap only): what the xyz wave of a bundle needs to do
+// k_touch_wave<kAxisCapSmall>'s work for the ray it has just written.  The path of ray m is parked in a slot of its own,
+// path[m * path_stride, + nsteps): no offset, so no scan in front of the walk.
+struct MergeWalk {
+  FrameBlocks blocks;
+  u32* path;        // the spare record-sort buffer, rec_cap words
+  u32 path_stride;  // IntegratorPlan::steps_max: no ray of the configuration has more steps
+  u32 rec_cap;
+  const u64* fh_keys;  // the bundle hash (anti-grazing)
+  u32 fh_mask;
+};
+
+// kWalk = false is the kernel as it was (its code is unchanged by the template: pieces, the walk in stage T or in a launch of its own)
+template <bool kWalk>
 __global__ void __launch_bounds__(256) k_bundle_merge(const FrameParams* __restrict__ Pp, BundleView V, const u32* __restrict__ bstart, RayArrays R, Counters* cnt,
-                                                      u32 piece_axis_cap) {
+                                                      u32 piece_axis_cap, MergeWalk walk) {
   const FrameParams P = *Pp;
   const u32 np2 = P.np2;
   const float* __restrict__ xyz = P.xyz;
@@ -578,16 +597,13 @@ __global__ void __launch_bounds__(256) k_bundle_merge(const FrameParams* __restr
       }
     } else {
       const float mx = readlane_f32(val, 0), my = readlane_f32(val, 1), mz = readlane_f32(val, 2);
-      if (lane == 0) {
-        const F3 pg = transform_point(P, F3{mx, my, mz});
-        Dda d;
-        dda_setup(d, P, pg, clearing);
+      auto write_ray = [&](const F3& pg, const Dda& d, u32 flags) {  // one lane
         if (d.range_error) atomicOr(&cnt->err, kErrRange);
         R.px[m] = pg.x;
         R.py[m] = pg.y;
         R.pz[m] = pg.z;
         R.w[m] = W;
-        R.flags[m] = 1u | (clearing ? 2u : 0u);
+        R.flags[m] = flags;
         R.key[m] = key;
         R.nsteps[m] = d.nsteps;
         if (piece_axis_cap) R.pbound[m] = piece_bound(d, piece_axis_cap);
@@ -599,6 +615,31 @@ __global__ void __launch_bounds__(256) k_bundle_merge(const FrameParams* __restr
           q[0] = F4{dv.x, dv.y, dv.z, sqrtf(dot3(dv, dv))};
           R.q[static_cast<size_t>(m) * 8u + 4u] = W;  // (word 5 is the colour, written by the bundle's colour wave)
         }
+      };
+      if constexpr (kWalk) {
+        // The ray is wave-uniform: every lane sets it up, lane 0 writes it, and the wave walks it here, in the shadow of the frame's
+        // longer bundles.  The walk's scratch (crossing times and path: 3 KB) is the wave's own operand table (4 KB), free since the
+        // last chunk's hand-over.
+        static_assert(6 * kAxisCapSmall * sizeof(u32) <= sizeof(ops[0]), "the walk's scratch fits the wave's operand table");
+        const F3 pg = transform_point(P, F3{mx, my, mz});
+        Dda d;
+        dda_setup(d, P, pg, clearing);
+        const u32 ns = d.nsteps;
+        // (a slot that would end beyond the record buffers: COX_RECORD_CAP only -- emit then walks the ray itself)
+        const bool fits = ns <= walk.path_stride && (static_cast<u64>(m) + 1ull) * walk.path_stride <= static_cast<u64>(walk.rec_cap);
+        const u32 flags = 1u | (clearing ? 2u : 0u) | (fits ? 0u : kRayNoPath);
+        if (lane == 0) write_ray(pg, d, flags);
+        if (ns != 0) {
+          float* tl = reinterpret_cast<float*>(tbl);
+          wave_touch_ray<kAxisCapSmall>(P, R, walk.blocks, m, ns, flags, d, key, tl, reinterpret_cast<u32*>(tl + 3 * kAxisCapSmall), lane,
+                                        fits ? walk.path + m * walk.path_stride : nullptr, cnt, walk.fh_keys, walk.fh_mask);
+          wave_lds_handover();  // (the sequential fallback leaves without one) the next task fills the operand table
+        }
+      } else if (lane == 0) {
+        const F3 pg = transform_point(P, F3{mx, my, mz});
+        Dda d;
+        dda_setup(d, P, pg, clearing);
+        write_ray(pg, d, 1u | (clearing ? 2u : 0u));
       }
     }
   }

@@ -137,8 +137,7 @@ __global__ void __launch_bounds__(256) k_emit(const FrameParams* __restrict__ Pp
 //     that would need more crossings of one axis than were generated) fall back to the sequential walk on lane 0.
 // per-axis crossing capacity of the parallel DDA: two instantiations, the small one (12 KB of LDS per workgroup instead
 // of 48 KB, so every ray of a frame is resident at once) whenever no ray of the configuration can cross more planes
-constexpr u32 kAxisCapSmall = 128, kAxisCapLarge = 512;
-constexpr u32 kRayFallback = 4u;  // ray flag
+// (kAxisCapSmall, kAxisCapLarge and the ray flags kRayFallback, kRayNoPath: cox_frame.hpp -- the bundle merge uses them too)
 
 __device__ __forceinline__ u32 pack_path(u32 jx, u32 jy, u32 jz) { return jx | (jy << 10) | (jz << 20); }
 // entries of the sorted array a[0, n) that precede t: a[i] < t, or a[i] <= t when inclusive
@@ -291,12 +290,7 @@ __device__ __forceinline__ u32 touch_block(const FrameParams& P, const LayerView
 // own (one per record set: open addressing on the packed block key, sized with the layer's table, so a frame that fits the layer's
 // fits the frame's) and touches no layer word.  The layer comes in with the binding (k_bind_blocks), one thread per touched block:
 // the only step of a frame that has to follow the previous frame's update.
-struct FrameBlocks {
-  u64* keys;   // [mask + 1] block key per slot; empty between frames (the binding empties the slots it reads)
-  u32* ord;    // [mask + 1] ordinal of the slot's key (valid while the key is there)
-  u32* slots;  // [mask + 1] the occupied slots in ordinal order: slots[0, n_touched)
-  u32 mask;
-};
+// (struct FrameBlocks: cox_frame.hpp, with the other views)
 // the first inserter of a key hands out its ordinal (the walk; emit runs in a later launch and only looks up)
 __device__ __forceinline__ void touch_frame_block(const FrameBlocks& B, u64 bkey, Counters* cnt) {
   bool fresh;
@@ -355,6 +349,58 @@ __global__ void __launch_bounds__(256) k_bind_blocks(LayerView L, FrameBlocks B,
   bind_touched_blocks(L, B, ord_info, cnt, layer_err);
 }
 
+// The wave walk of ONE ray, for every kernel that touches from it (k_touch_wave; k_bundle_merge<true>, on the wave that has just
+// produced the ray): the parallel path into `tl` / `path` (LDS, this wave's: 3 * kAxisCap words each), the ray's flags, its path
+// parked at `park` (nullptr: not parked) for k_emit_wave, and its blocks into the frame block table.  Every argument is wave-uniform
+// and `d` is the ray's dda_setup; `flags` comes in without kRayFallback.
+template <u32 kAxisCap>
+__device__ void wave_touch_ray(const FrameParams& P, const RayArrays& R, const FrameBlocks& B, u32 r, u32 ns, u32 flags, Dda d, u64 own_key, float* tl, u32* path,
+                               u32 lane, u32* __restrict__ park, Counters* cnt, const u64* __restrict__ fh_keys, u32 fh_mask) {
+  const bool clearing = (flags & 2u) != 0;
+  const bool par = wave_ray_path<kAxisCap>(d, ns, tl, path, lane);
+  if (lane == 0) R.flags[r] = par ? flags : (flags | kRayFallback);
+  if (par) {
+    u64 carry = kEmptyKey;
+    for (u32 base = 0; base < ns; base += 64) {
+      const u32 s = base + lane;
+      const bool act = s < ns;
+      u64 bkey = kEmptyKey;
+      bool skip = false;
+      if (act) {
+        const u32 p = path[s];
+        if (park) park[s] = p;  // emit reads the walk instead of redoing it
+        const int x = d.c[0] + static_cast<int>(p & 1023u) * d.sgn[0];
+        const int y = d.c[1] + static_cast<int>((p >> 10) & 1023u) * d.sgn[1];
+        const int z = d.c[2] + static_cast<int>(p >> 20) * d.sgn[2];
+        skip = grazing_skip(P, fh_keys, fh_mask, clearing, own_key, x, y, z);
+        bkey = pack_key(x >> 4, y >> 4, z >> 4);
+      }
+      // a voxel touches its block unless the previous voxel THAT WAS NOT SKIPPED lies in the same block (a block whose
+      // first voxel on the ray is skipped by anti-grazing must still be allocated by the next one; found by the fuzzer)
+      const u64 kept = __ballot(act && !skip);
+      const u64 kept_below = kept & ((1ull << lane) - 1ull);
+      const int src = kept_below ? (63 - __clzll(static_cast<long long>(kept_below))) : 0;
+      const u64 prev_kept = __shfl(bkey, src, 64);
+      const u64 prev = kept_below ? prev_kept : carry;
+      if (act && !skip && bkey != prev) touch_frame_block(B, bkey, cnt);
+      if (kept) carry = __shfl(bkey, 63 - __clzll(static_cast<long long>(kept)), 64);
+    }
+    wave_lds_handover();  // the next user of this wave's LDS scratch
+  } else if (lane == 0) {
+    // sequential fallback
+    u64 last_bkey = kEmptyKey;
+    for (u32 s = 0; s < ns; ++s) {
+      const int x = d.c[0], y = d.c[1], z = d.c[2];
+      dda_step(d);
+      if (grazing_skip(P, fh_keys, fh_mask, clearing, own_key, x, y, z)) continue;
+      const u64 bkey = pack_key(x >> 4, y >> 4, z >> 4);
+      if (bkey == last_bkey) continue;
+      last_bkey = bkey;
+      touch_frame_block(B, bkey, cnt);
+    }
+  }
+}
+
 template <u32 kAxisCap>
 __global__ void __launch_bounds__(256) k_touch_wave(const FrameParams* __restrict__ Pp, RayArrays R, FrameBlocks B, u32* __restrict__ path_out, u32 rec_cap, Counters* cnt,
                                                     const u64* __restrict__ fh_keys, u32 fh_mask) {
@@ -371,61 +417,21 @@ __global__ void __launch_bounds__(256) k_touch_wave(const FrameParams* __restric
   for (u32 r = uniform_u32((blockIdx.x * blockDim.x + threadIdx.x) >> 6); r < n_slots; r += waves_total) {
     const u32 ns = uniform_u32(R.nsteps[r]);
     if (ns == 0) continue;
-    const u32 flags = uniform_u32(R.flags[r]);
-    const bool clearing = (flags & 2u) != 0;
+    const u32 flags = uniform_u32(R.flags[r]) & ~(kRayFallback | kRayNoPath);
     const F3 pg{readlane_f32(R.px[r], 0), readlane_f32(R.py[r], 0), readlane_f32(R.pz[r], 0)};
     const u64 own_key = P.anti_grazing ? R.key[r] : 0ull;
+    const u32 off = uniform_u32(R.rec_off[r]);
     Dda d;
-    dda_setup(d, P, pg, clearing);
-    const bool par = wave_ray_path<kAxisCap>(d, ns, tl, path, lane);
-    if (lane == 0) R.flags[r] = par ? (flags & ~kRayFallback) : (flags | kRayFallback);
-    if (par) {
-      const u32 off = uniform_u32(R.rec_off[r]);
-      u64 carry = kEmptyKey;
-      for (u32 base = 0; base < ns; base += 64) {
-        const u32 s = base + lane;
-        const bool act = s < ns;
-        u64 bkey = kEmptyKey;
-        bool skip = false;
-        if (act) {
-          const u32 p = path[s];
-          if (!overflow) path_out[off + s] = p;  // emit reads the walk instead of redoing it
-          const int x = d.c[0] + static_cast<int>(p & 1023u) * d.sgn[0];
-          const int y = d.c[1] + static_cast<int>((p >> 10) & 1023u) * d.sgn[1];
-          const int z = d.c[2] + static_cast<int>(p >> 20) * d.sgn[2];
-          skip = grazing_skip(P, fh_keys, fh_mask, clearing, own_key, x, y, z);
-          bkey = pack_key(x >> 4, y >> 4, z >> 4);
-        }
-        // a voxel touches its block unless the previous voxel THAT WAS NOT SKIPPED lies in the same block (a block whose
-        // first voxel on the ray is skipped by anti-grazing must still be allocated by the next one; found by the fuzzer)
-        const u64 kept = __ballot(act && !skip);
-        const u64 kept_below = kept & ((1ull << lane) - 1ull);
-        const int src = kept_below ? (63 - __clzll(static_cast<long long>(kept_below))) : 0;
-        const u64 prev_kept = __shfl(bkey, src, 64);
-        const u64 prev = kept_below ? prev_kept : carry;
-        if (act && !skip && bkey != prev) touch_frame_block(B, bkey, cnt);
-        if (kept) carry = __shfl(bkey, 63 - __clzll(static_cast<long long>(kept)), 64);
-      }
-      wave_lds_handover();  // the next ray of this wave reuses the LDS scratch
-    } else if (lane == 0) {
-      // sequential fallback
-      u64 last_bkey = kEmptyKey;
-      for (u32 s = 0; s < ns; ++s) {
-        const int x = d.c[0], y = d.c[1], z = d.c[2];
-        dda_step(d);
-        if (grazing_skip(P, fh_keys, fh_mask, clearing, own_key, x, y, z)) continue;
-        const u64 bkey = pack_key(x >> 4, y >> 4, z >> 4);
-        if (bkey == last_bkey) continue;
-        last_bkey = bkey;
-        touch_frame_block(B, bkey, cnt);
-      }
-    }
+    dda_setup(d, P, pg, (flags & 2u) != 0);
+    wave_touch_ray<kAxisCap>(P, R, B, r, ns, flags, d, own_key, tl, path, lane, overflow ? nullptr : path_out + off, cnt, fh_keys, fh_mask);
   }
 }
 
+// path_stride: where the walk parked ray r's path -- 0: at its record offset, path_in[rec_off[r] + s] (k_touch_wave); otherwise in a
+// slot of that many words of the ray's own, path_in[r * path_stride + s] (k_bundle_merge<true>, which runs ahead of the offsets' scan)
 __global__ void __launch_bounds__(256) k_emit_wave(const FrameParams* __restrict__ Pp, RayArrays R, FrameBlocks B, const u32* __restrict__ path_in, u32* __restrict__ rec_key,
                                                    u32* __restrict__ rec_ray, u32 rec_cap, Counters* cnt, SortInfo* sort_info,
-                                                   const u64* __restrict__ fh_keys, u32 fh_mask, int by_block) {
+                                                   const u64* __restrict__ fh_keys, u32 fh_mask, int by_block, u32 path_stride) {
   const FrameParams P = *Pp;
   const u32 n_slots = uniform_u32(cnt->n_ray_slots);
   const bool overflow = uniform_u32(cnt->n_records) > rec_cap;
@@ -452,7 +458,8 @@ __global__ void __launch_bounds__(256) k_emit_wave(const FrameParams* __restrict
     const u64 own_key = P.anti_grazing ? R.key[r] : 0ull;
     Dda d;
     dda_setup(d, P, pg, clearing);
-    if (!(flags & kRayFallback)) {
+    if (!(flags & (kRayFallback | kRayNoPath))) {
+      const u32 pbase = path_stride ? r * path_stride : off;
       u64 carry_key = kEmptyKey;
       u32 carry_ord = kInvalid;
       for (u32 base = 0; base < ns; base += 64) {
@@ -462,7 +469,7 @@ __global__ void __launch_bounds__(256) k_emit_wave(const FrameParams* __restrict
         bool skip = false;
         u32 lin = 0;
         if (act) {
-          const u32 p = path_in[off + s];
+          const u32 p = path_in[pbase + s];
           const int x = d.c[0] + static_cast<int>(p & 1023u) * d.sgn[0];
           const int y = d.c[1] + static_cast<int>((p >> 10) & 1023u) * d.sgn[1];
           const int z = d.c[2] + static_cast<int>(p >> 20) * d.sgn[2];

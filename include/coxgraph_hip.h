@@ -233,11 +233,11 @@ int cox_integrator_host_time(cox_integrator_t* integ, double* ms_total, uint64_t
  * reset, regions[k] = how many regions that is (one region = the consecutive launches of that class in one frame; the
  * sweeps of the fast integrator are one region per round) */
 typedef enum cox_kernel_class {
-  COX_KC_MERGE = 0,       /* k_bundle_merge (merged: the bundles' sequential means) */
+  COX_KC_MERGE = 0,       /* k_bundle_merge (merged: the bundles' sequential means; where the merge walks the rays it writes -- COX_TOUCH, DESIGN.md section 5 -- the touch as well) */
   COX_KC_APPLY = 1,       /* k_apply_eval + k_apply_long (the TSDF update) */
   COX_KC_BUNDLE_HASH = 2, /* frame hash memset + k_bundle_insert + k_bundle_keys (merged) */
   COX_KC_POINT_SORT = 3,  /* radix sort of the points (merged: bundling) */
-  COX_KC_TOUCH_EMIT = 4,  /* record offsets + touch (block allocation) + emit */
+  COX_KC_TOUCH_EMIT = 4,  /* record offsets + touch (block allocation) + emit (emit alone where the merge walks the rays) */
   COX_KC_RECORD_SORT = 5, /* radix sort of the (voxel, ray) records */
   COX_KC_FAST_START = 6,  /* fast: start-set sort + flags + ray list */
   COX_KC_FAST_VISITS = 7, /* fast: candidate visits + their sort + inverse */
