@@ -8,7 +8,8 @@
 //                   integers reach the record by integer atomics (order-free), sum r^2 goes to cost_part[candidate][chunk].
 //   k_align_finish  one wave per candidate sums its chunk partials (and the chunks' sums of weights) in an order that
 //                   depends on the chunk count alone, and writes cost.
-// The per-point value is cox_reg.hpp's reg_cell / reg_value: the same bits as the registration cost.
+// The per-point value is cox_reg.hpp's reg_cell / reg_value (point_cell of cox_interp.hpp under the candidate's transform):
+// the same bits as the registration cost.  The wave sums are cox_device.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -62,17 +63,6 @@ __device__ __forceinline__ void align_point(const LayerView& L, const float* R, 
     a.k += (inlier && k > 0) ? static_cast<u32>(k) : 0u;
   }
   a.s += r * r;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {  // lanes pairwise, the same tree every time
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ u32 wave_sum_u32(u32 v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
 }
 
 __global__ void __launch_bounds__(kAlignThreads) k_align_sweep(LayerView L, const float* __restrict__ pts, const u32* __restrict__ sample_idx, u32 m,

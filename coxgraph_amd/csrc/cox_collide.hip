@@ -50,12 +50,11 @@ __device__ __forceinline__ float dot_self(float x, float y, float z) { return (x
 
 // rule S: COX_C_* of the sample p; *dist holds the trilinear distance when COX_C_DISTANCE is set
 __device__ __forceinline__ u32 sample_state(const LayerView& L, const CollideParams& P, const float p[3], float* dist) {
-  float sc[3];
-  if (!block_scaled(L, p, sc)) return COX_C_INVALID;  // NaN, +-inf, beyond the keys
+  if (!point_in_range(L, p)) return COX_C_INVALID;  // NaN, +-inf, beyond the keys
   // the trilinear cell reaches g - 1 .. g + 1, one more voxel on each side for rounding at block faces; the nearest voxel is g
-  BlockCache bc{L, {0, 0, 0}, {kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid}, 0u};
+  BlockCache bc{L, kNoBlocks};
   int b[3];
-  block_cache_fill<2>(L, p, sc, bc, b);
+  block_cache_fill<2>(L, p, bc, b);
   float d = 0.0f, w = 0.0f;
   if (nearest_sample(L, bc, p, &d, &w)) {  // EsdfMap::isObserved
     float dv = 0.0f, wv = 0.0f;

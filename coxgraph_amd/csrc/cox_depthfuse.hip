@@ -165,8 +165,7 @@ __global__ void __launch_bounds__(kDfThreads) k_df_valid(const float* __restrict
   __shared__ u32 part[kDfThreads / 64];
   u32 mine = 0;
   for (u32 i = blockIdx.x * kDfThreads + threadIdx.x; i < n_px; i += gridDim.x * kDfThreads) mine += valid_depth(depth[i]) ? 1u : 0u;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
+  mine = wave_sum_u32(mine);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -287,11 +286,8 @@ __global__ void __launch_bounds__(kDfThreads) k_df_update(DfParams P, const floa
     word[1] = __float_as_uint(std_min(P.max_weight, nw));
     ++n_upd;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    n_upd += __shfl_down(n_upd, off, 64);
-    n_col += __shfl_down(n_col, off, 64);
-  }
+  n_upd = wave_sum_u32(n_upd);
+  n_col = wave_sum_u32(n_col);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = n_upd, part[4 + (threadIdx.x >> 6)] = n_col;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -127,6 +127,23 @@ __device__ __forceinline__ void wave_lds_handover() {
 
 __device__ __forceinline__ u32 lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
+// sum over the 64 lanes of a wave, valid in lane 0: lanes pairwise, the same tree every time
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ u32 wave_sum_u32(u32 v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
 // ---- open-addressing hash set/map on packed keys -------------------------------------------
 // insert-or-find; returns the slot, *fresh = true when this thread claimed it.
 // The slot is first read with an agent-scope load (served past the non-coherent L1): thousands of

@@ -28,6 +28,7 @@
 #include "../../include/coxgraph_hip.h"
 #include "cox_device.hpp"
 #include "cox_host.hpp"
+#include "cox_interp.hpp"
 
 using namespace cox;
 
@@ -583,7 +584,7 @@ __global__ void __launch_bounds__(256) k_relevant_count(const u32* __restrict__ 
   const u32* blk = voxels + static_cast<size_t>(blockIdx.x) * kVoxelsPerBlock * kWordsPerVoxel;
   u32 c = 0;
   for (u32 v = threadIdx.x; v < kVoxelsPerBlock; v += 256) c += relevant_voxel(blk + 3 * v, min_w, max_d) ? 1u : 0u;
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+  c = wave_sum_u32(c);
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(&total, c);
   __syncthreads();
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
@@ -715,76 +716,29 @@ extern "C" int cox_regpoints_from_layer(cox_layer_t* L, float min_voxel_weight, 
 // B's grid (transformLayer: candidate output blocks from the transformed block centres, every output voxel centre taken
 // back into A and interpolated trilinearly, nearest voxel if that fails, blocks without data dropped), then merged
 // voxel by voxel (mergeVoxelAIntoVoxelB).
-struct LayerConstView {
-  const u32* voxels;
-  const u64* ht_keys;
-  const u32* ht_vals;
-  u32 ht_mask;
-  float voxel_size, voxel_size_inv, block_size, block_size_inv;
-};
 struct RigidParams {
   float qw, qx, qy, qz, tx, ty, tz;
 };
 __device__ __forceinline__ F3 rigid_apply(const RigidParams& T, F3 v) {
   return quat_transform(T.qw, T.qx, T.qy, T.qz, F3{T.tx, T.ty, T.tz}, v);
 }
-__constant__ float c_merge_interp_table[8][8] = {{1, 0, 0, 0, 0, 0, 0, 0},   {-1, 0, 0, 0, 1, 0, 0, 0},   {-1, 0, 1, 0, 0, 0, 0, 0},
-                                                 {-1, 1, 0, 0, 0, 0, 0, 0},  {1, 0, -1, 0, -1, 0, 1, 0},  {1, -1, -1, 1, 0, 0, 0, 0},
-                                                 {1, -1, 0, 0, -1, 1, 0, 0}, {-1, 1, 1, -1, 1, -1, -1, 1}};
-__device__ __forceinline__ float interp_member(const float q[8], const float data[8]) {
-  float md[8];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    float s = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) s += c_merge_interp_table[r][c] * data[c];
-    md[r] = s;
-  }
-  float v = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) v += q[i] * md[i];
-  return v;
-}
-__device__ __forceinline__ const u32* voxel_words(const LayerConstView& L, u32 pool, int vx, int vy, int vz) {
-  return L.voxels + (static_cast<size_t>(pool) * kVoxelsPerBlock + static_cast<u32>(vx + 16 * (vy + 16 * vz))) * kWordsPerVoxel;
-}
-// Interpolator::getVoxel(pos, &voxel, true) || getVoxel(pos, &voxel, false); returns false when neither is possible
-__device__ __forceinline__ bool resample_voxel(const LayerConstView& L, const float pos[3], u32 out[3]) {
-  float sc[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) sc[k] = pos[k] * L.block_size_inv;
-  if (!(index_in_range(sc[0]) && index_in_range(sc[1]) && index_in_range(sc[2]))) return false;
+// Interpolator::getVoxel(pos, &voxel, true) || getVoxel(pos, &voxel, false); returns false when neither is possible.  The cell
+// is cox_interp.hpp's cell_corner; the gather stays here because it also reads the colour word and stops at the first miss.
+__device__ __forceinline__ bool resample_voxel(const LayerView& L, const float pos[3], u32 out[3]) {
+  if (!point_in_range(L, pos)) return false;
   int b0[3], v0[3];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) b0[k] = grid_index(sc[k]);
-  const u32 slot0 = ht_find(L.ht_keys, L.ht_mask, pack_key(b0[0], b0[1], b0[2]));
-  if (slot0 == kInvalid) return false;
-  const u32 pool0 = L.ht_vals[slot0];
+  for (int k = 0; k < 3; ++k) locate(L, pos[k], &b0[k], &v0[k]);
+  const HtPool find{L};
+  const u32 pool0 = find(b0[0], b0[1], b0[2]);
   if (pool0 == kInvalid) return false;
-  int b[3], vi[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float origin = static_cast<float>(b0[k]) * L.block_size;
-    int v = grid_index((pos[k] - origin) * L.voxel_size_inv);
-    v = v > 15 ? 15 : (v < 0 ? 0 : v);
-    v0[k] = v;
-    b[k] = b0[k];
-    const float c = origin + center_coord(v, L.voxel_size);
-    if (pos[k] - c < 0.0f) {
-      v--;
-      if (v < 0) {
-        b[k]--;
-        v += 16;
-      }
-    }
-    vi[k] = v;
-  }
+  int b[3] = {b0[0], b0[1], b0[2]}, vi[3];
+  cell_corner(L, pos, b, vi);
   // ---- trilinear ----
   bool ok = true;
   u32 base_pool = pool0;
   if (b[0] != b0[0] || b[1] != b0[1] || b[2] != b0[2]) {
-    const u32 sl = ht_find(L.ht_keys, L.ht_mask, pack_key(b[0], b[1], b[2]));
-    base_pool = (sl == kInvalid) ? kInvalid : L.ht_vals[sl];
+    base_pool = find(b[0], b[1], b[2]);
     ok = base_pool != kInvalid;
   }
   float d[8], w[8], ch[4][8];
@@ -804,14 +758,13 @@ __device__ __forceinline__ bool resample_voxel(const LayerConstView& L, const fl
         }
       u32 pool = base_pool;
       if (moved) {
-        const u32 sl = ht_find(L.ht_keys, L.ht_mask, pack_key(nb[0], nb[1], nb[2]));
-        pool = (sl == kInvalid) ? kInvalid : L.ht_vals[sl];
+        pool = find(nb[0], nb[1], nb[2]);
         if (pool == kInvalid) {
           ok = false;
           break;
         }
       }
-      const u32* vw = voxel_words(L, pool, v[0], v[1], v[2]);
+      const u32* vw = voxel_ptr(L, pool, v[0], v[1], v[2]);
       const float wi = __uint_as_float(vw[1]);
       if (!(wi > 0.0f)) {
         ok = false;
@@ -828,29 +781,23 @@ __device__ __forceinline__ bool resample_voxel(const LayerConstView& L, const fl
   }
   if (ok) {
     float off[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float c0 = static_cast<float>(b[k]) * L.block_size + center_coord(vi[k], L.voxel_size);
-      off[k] = (pos[k] - c0) * L.voxel_size_inv;
-    }
-    const float dx = off[0], dy = off[1], dz = off[2];
-    const float q[8] = {1.0f, dx, dy, dz, dx * dy, dy * dz, dz * dx, dx * dy * dz};
-    out[0] = __float_as_uint(interp_member(q, d));
-    out[1] = __float_as_uint(interp_member(q, w));
-    const u32 r = static_cast<u32>(static_cast<int>(interp_member(q, ch[0]))) & 255u, g = static_cast<u32>(static_cast<int>(interp_member(q, ch[1]))) & 255u;
-    const u32 bl = static_cast<u32>(static_cast<int>(interp_member(q, ch[2]))) & 255u, a = static_cast<u32>(static_cast<int>(interp_member(q, ch[3]))) & 255u;
+    cell_offset(L, pos, b, vi, off);
+    out[0] = __float_as_uint(interp_member(off, d));
+    out[1] = __float_as_uint(interp_member(off, w));
+    const u32 r = static_cast<u32>(static_cast<int>(interp_member(off, ch[0]))) & 255u, g = static_cast<u32>(static_cast<int>(interp_member(off, ch[1]))) & 255u;
+    const u32 bl = static_cast<u32>(static_cast<int>(interp_member(off, ch[2]))) & 255u, a = static_cast<u32>(static_cast<int>(interp_member(off, ch[3]))) & 255u;
     out[2] = a | (bl << 8) | (g << 16) | (r << 24);
     return true;
   }
   // ---- nearest voxel of the block that contains pos ----
-  const u32* vw = voxel_words(L, pool0, v0[0], v0[1], v0[2]);
+  const u32* vw = voxel_ptr(L, pool0, v0[0], v0[1], v0[2]);
   out[0] = vw[0];
   out[1] = vw[1];
   out[2] = vw[2];
   return true;
 }
 // one workgroup per candidate output block
-__global__ void __launch_bounds__(256) k_resample_blocks(LayerConstView A, RigidParams T_in_out, const int32_t* __restrict__ cand_idx, float voxel_size_out,
+__global__ void __launch_bounds__(256) k_resample_blocks(cox::LayerView A, RigidParams T_in_out, const int32_t* __restrict__ cand_idx, float voxel_size_out,
                                                          float block_size_out, u32* __restrict__ tmp, u32* __restrict__ has_data) {
   const u32 c = blockIdx.x;
   const float ox = static_cast<float>(cand_idx[3 * c]) * block_size_out, oy = static_cast<float>(cand_idx[3 * c + 1]) * block_size_out,
@@ -984,7 +931,7 @@ extern "C" int cox_layer_merge(const cox_layer_t* A_, const float T_B_A[7], cox_
     COX_HIP(hipMemcpy(d_cand, cand.data(), sizeof(int32_t) * cand.size(), hipMemcpyHostToDevice));
     COX_HIP(hipMemset(d_has, 0, sizeof(u32) * nc));
     COX_HIP(hipMemset(d_tmp, 0, sizeof(u32) * block_words * nc));
-    const LayerConstView AV{A->voxels, A->ht_keys, A->ht_vals, A->ht_cap - 1, A->voxel_size, A->voxel_size_inv, A->block_size, A->block_size_inv};
+    const cox::LayerView AV = layer_view(A);
     hipLaunchKernelGGL(k_resample_blocks, dim3(nc), dim3(256), 0, nullptr, AV, Tinv, d_cand, B->voxel_size, B->block_size, d_tmp, d_has);
     std::vector<u32> has(nc);
     COX_HIP(hipMemcpy(has.data(), d_has, sizeof(u32) * nc, hipMemcpyDeviceToHost));

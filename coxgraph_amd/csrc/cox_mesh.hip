@@ -135,12 +135,7 @@ __global__ void __launch_bounds__(256) k_tri_count(MeshView M, u32* __restrict__
   }
   if (err) atomicOr(d_err, err);
   // totals in 64 bit (the 32-bit scans below are only trusted once these fit)
-  u64 a = npts, b = npairs, c = static_cast<u64>(npts) * npairs;
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_down(a, off);
-    b += __shfl_down(b, off);
-    c += __shfl_down(c, off);
-  }
+  const u64 a = wave_sum_u64(npts), b = wave_sum_u64(npairs), c = wave_sum_u64(static_cast<u64>(npts) * npairs);
   if (lane_id() == 0 && (a | b | c)) {
     atomicAdd(reinterpret_cast<unsigned long long*>(&totals[0]), static_cast<unsigned long long>(a));
     atomicAdd(reinterpret_cast<unsigned long long*>(&totals[1]), static_cast<unsigned long long>(b));

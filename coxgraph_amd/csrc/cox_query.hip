@@ -4,9 +4,10 @@
 // voxblox's EsdfMap / TsdfMap / Interpolator):
 //
 //   k_query<MODE, GRAD>  one lane per query, queries in input order, outputs coalesced.  The <= 8 blocks a query can touch
-//                        (its 7 samples lie in voxels v0 - 1 .. v0 + 2 on each axis) are resolved with ht_find once, up front;
-//                        a sample whose cell falls outside that set (float rounding) looks its block up afresh.  Each sample's
-//                        cell is interp_cell (cox_interp.hpp, shared with the registration): 16 independent voxel loads.
+//                        (its 7 samples lie in voxels v0 - 1 .. v0 + 2 on each axis) are resolved once, up front, into a
+//                        BlockCache of cox_interp.hpp (block_cache_fill's body, in place); a sample whose cell falls outside
+//                        that set (float rounding) looks its block up afresh.  The samples are tri_sample / nearest_sample of
+//                        the same header: each cell is interp_cell, 16 independent voxel loads.
 //   k_free_count         createFreePointcloudFromEsdfLayer, pass 1: per block (download order) the voxels that pass
 //   exclusive_scan_u32   block offsets (cox_sort.hpp)
 //   k_free_write         pass 2: voxel centres + distances, linear voxel order inside a block
@@ -85,23 +86,23 @@ __global__ void __launch_bounds__(kQueryThreads) k_query(LayerView L, const floa
   // the blocks of voxels g - r .. g + r around the voxel g that contains p: the samples reach g - 2 .. g + 2 (g - 1 .. g + 1
   // without a gradient), one more voxel on each side for rounding at block faces
   constexpr int r = GRAD ? 3 : (MODE == COX_QUERY_NEAREST ? 1 : 2);
-  BlockCache bc{L, {0, 0, 0}, {kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid}, 0u};
+  BlockCache bc{L, kNoBlocks};
+  // block_cache_fill<r>'s body, kept in place: through the call ADAPTIVE without a gradient takes 66 VGPRs for 64 and loses a wave
   int span[3], b[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     b[k] = grid_index(sc[k]);
     const int v = grid_index((p[k] - static_cast<float>(b[k]) * L.block_size) * L.voxel_size_inv);
     const int g = b[k] * 16 + (v > 15 ? 15 : (v < 0 ? 0 : v));
-    bc.lo[k] = (g - r) >> 4;
-    span[k] = ((g + r) >> 4) - bc.lo[k];
+    bc.s.lo[k] = (g - r) >> 4;
+    span[k] = ((g + r) >> 4) - bc.s.lo[k];
   }
-  // only the blocks the range touches: one lookup for a query deep inside a block
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     const int mx = (c >> 2) & 1, my = (c >> 1) & 1, mz = c & 1;
     if (mx <= span[0] && my <= span[1] && mz <= span[2]) {
-      bc.pool[c] = HtPool{L}(bc.lo[0] + mx, bc.lo[1] + my, bc.lo[2] + mz);
-      bc.have |= 1u << c;
+      bc.s.pool[c] = HtPool{L}(bc.s.lo[0] + mx, bc.s.lo[1] + my, bc.s.lo[2] + mz);
+      bc.s.have |= 1u << c;
     }
   }
   const bool own_block = !GRAD || bc(b[0], b[1], b[2]) != kInvalid;  // getGradient: getBlockPtrByCoordinates(pos)

@@ -8,8 +8,10 @@
 //   cox_reg_evaluate   Ceres-shaped: residuals[n], two row-major n x 4 Jacobians
 //   cox_reg_normal_eq  fused: per-point residual + Jacobian rows stay in registers / LDS; each wave
 //                      accumulates sum x x^T for x = [J_ref(4) J_read(4) r 1 w has_corr] with
-//                      v_mfma_f64_16x16x4_f64 (the only MFMA use in the engine), partials are summed
-//                      in a fixed order, so H, b, cost are reproducible run to run.
+//                      v_mfma_f64_16x16x4_f64 (cox_normal_eq.hpp), partials are summed in a fixed
+//                      order, so H, b, cost are reproducible run to run.
+//
+// The cell, the trilinear value and its gradient are cox_interp.hpp's; cox_reg.hpp holds the relative pose.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +23,7 @@
 #include "cox_device.hpp"
 #include "cox_host.hpp"
 #include "cox_interp.hpp"
+#include "cox_normal_eq.hpp"
 #include "cox_reg.hpp"
 
 using namespace cox;
@@ -34,7 +37,7 @@ struct PointResult {
   bool has;
 };
 
-// voxblox Interpolator<TsdfVoxel>::getVoxelsAndQVector + trilinear value/gradient, then the voxgraph residual
+// the cell of the point in the reading layer, its trilinear value and gradient, then the voxgraph residual
 __device__ __forceinline__ PointResult reg_point(const ReadingView& L, const RelPose& P, const float* __restrict__ pt, double no_corr_cost) {
   PointResult o;
   const float px = pt[0], py = pt[1], pz = pt[2], pd = pt[3], pw = pt[4];
@@ -45,24 +48,11 @@ __device__ __forceinline__ PointResult reg_point(const ReadingView& L, const Rel
   for (int k = 0; k < 8; ++k) o.J[k] = 0.0;
   float md[8], off[3];
   if (!reg_cell(L, P.R, P.t, px, py, pz, md, off)) return o;
-  const float dx = off[0], dy = off[1], dz = off[2];
-  const float qx[8] = {0, 1, 0, 0, dy, 0, dz, dy * dz};
-  const float qy[8] = {0, 0, 1, 0, dx, dz, 0, dz * dx};
-  const float qz[8] = {0, 0, 0, 1, 0, dy, dx, dx * dy};
-  const float val = reg_value(md, off);
-  float gxf = 0.0f, gyf = 0.0f, gzf = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    gxf += qx[i] * md[i];
-    gyf += qy[i] * md[i];
-    gzf += qz[i] * md[i];
-  }
-  gxf *= L.voxel_size_inv;
-  gyf *= L.voxel_size_inv;
-  gzf *= L.voxel_size_inv;
+  float val, g[3];
+  interp_value_gradient(md, off, L.voxel_size_inv, &val, g);
   o.has = true;
   o.r = static_cast<double>((pd - val) * pw);
-  const double w = pw, gx = gxf, gy = gyf, gz = gzf;
+  const double w = pw, gx = g[0], gy = g[1], gz = g[2];
   const double gRx = gx * P.cr - gy * P.sr, gRy = gx * P.sr + gy * P.cr, gRz = gz;
   const double dRfp_x = -P.sf * px - P.cf * py, dRfp_y = P.cf * px - P.sf * py;
   const double qxx = (P.cf * px - P.sf * py) + P.tf[0] - P.tr[0], qyy = (P.sf * px + P.cf * py) + P.tf[1] - P.tr[1];
@@ -79,8 +69,8 @@ __device__ __forceinline__ PointResult reg_point(const ReadingView& L, const Rel
 }
 
 // ---- Ceres-shaped evaluation ------------------------------------------------------------------------
-constexpr int kRegThreads = 256;
-constexpr int kPartial = 256;  // one 16x16 f64 tile per workgroup
+constexpr int kRegThreads = kNeqThreads;
+constexpr int kPartial = kNeqTile;  // one 16x16 f64 tile per workgroup
 
 __global__ void __launch_bounds__(kRegThreads) k_reg_evaluate(ReadingView L, RelPose P, const float* __restrict__ pts, const u32* __restrict__ sample_idx,
                                                               u32 n_res, double no_corr_cost, double* __restrict__ res, double* __restrict__ jf,
@@ -103,8 +93,7 @@ __global__ void __launch_bounds__(kRegThreads) k_reg_evaluate(ReadingView L, Rel
     }
   }
   // deterministic sum of the reference weights: lanes in order, waves in order, blocks on the host side
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
+  w = wave_sum_f64(w);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = w;
   __syncthreads();
   if (threadIdx.x == 0) block_w[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
@@ -123,14 +112,12 @@ __global__ void __launch_bounds__(256) k_reg_scale(double* __restrict__ a, size_
 }
 
 // ---- fused normal equations ----------------------------------------------------------------------------
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
+// x = [J_ref(4) J_read(4) r 1 w has_corr 0 0 0 0] per point; the sum and its reduction are cox_normal_eq.hpp's
 // (bx of nb: this workgroup's place among the workgroups of ITS constraint -- the whole grid for one constraint, a row of it in a batch)
 __device__ __forceinline__ void reg_normal_eq_body(const ReadingView& L, const RelPose& P, const float* __restrict__ pts, const u32* __restrict__ sample_idx, u32 n_res,
                                                    double no_corr_cost, double* partials /*[nb][256]*/, double* __restrict__ out /*[256]*/, u32* ticket, u32 bx, u32 nb) {
-  __shared__ double X[kRegThreads / 64][16][68];  // per wave: 16 components x 64 points (rows padded to 68: conflict-free writes, 2-way reads)
-  __shared__ double tile[kRegThreads / 64][256];
-  const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  __shared__ double X[kNeqWaves][16][kNeqRow];
+  __shared__ double tile[kNeqWaves][kNeqTile];
   double4_t acc = {0.0, 0.0, 0.0, 0.0};
   const u32 stride = nb * blockDim.x;
   const u32 n_iter = (n_res + stride - 1) / stride;
@@ -149,47 +136,10 @@ __device__ __forceinline__ void reg_normal_eq_body(const ReadingView& L, const R
       x[10] = static_cast<double>(o.w);
       x[11] = o.has ? 1.0 : 0.0;
     }
-#pragma unroll
-    for (int k = 0; k < 16; ++k) X[wave][k][lane] = x[k];
-    __builtin_amdgcn_wave_barrier();
-    // sum_p x_p x_p^T over this wave's 64 points: 16 MFMA steps of K = 4 points each.
-    // f64 16x16x4 operand map: lane l supplies A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15].
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const double a = X[wave][lane & 15u][4 * t + (lane >> 4)];
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, a, acc, 0, 0, 0);
-    }
-    __builtin_amdgcn_wave_barrier();
+    normal_eq_wave_step(X, x, acc);
   }
-  // f64 C/D map: col = lane & 15, row = (lane >> 4) + 4 * reg
-#pragma unroll
-  for (int r = 0; r < 4; ++r) tile[wave][((lane >> 4) + 4 * r) * 16 + (lane & 15u)] = acc[r];
-  __syncthreads();
-  partials[static_cast<size_t>(bx) * kPartial + threadIdx.x] =
-      ((tile[0][threadIdx.x] + tile[1][threadIdx.x]) + tile[2][threadIdx.x]) + tile[3][threadIdx.x];
-  // the workgroup that finishes last sums the partials of all workgroups in workgroup order: same bits every run, and no
-  // second launch (the one-workgroup reduction kernel took longer than this kernel)
-  __shared__ u32 last;
-  __threadfence();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const u32 t = atomicAdd(ticket, 1u);
-    last = (t == nb - 1u) ? 1u : 0u;
-    if (last) *ticket = 0u;  // ready for the next launch on this stream
-  }
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;  // four independent chains; the order of the additions stays fixed
-  u32 bq = 0;
-  for (; bq + 4 <= nb; bq += 4) {
-    s0 += __builtin_nontemporal_load(&partials[static_cast<size_t>(bq) * kPartial + threadIdx.x]);
-    s1 += __builtin_nontemporal_load(&partials[static_cast<size_t>(bq + 1) * kPartial + threadIdx.x]);
-    s2 += __builtin_nontemporal_load(&partials[static_cast<size_t>(bq + 2) * kPartial + threadIdx.x]);
-    s3 += __builtin_nontemporal_load(&partials[static_cast<size_t>(bq + 3) * kPartial + threadIdx.x]);
-  }
-  for (; bq < nb; ++bq) s0 += __builtin_nontemporal_load(&partials[static_cast<size_t>(bq) * kPartial + threadIdx.x]);
-  out[threadIdx.x] = (s0 + s1) + (s2 + s3);
+  double total;
+  if (normal_eq_finish(tile, acc, partials, ticket, bx, nb, &total)) out[threadIdx.x] = total;
 }
 
 __global__ void __launch_bounds__(kRegThreads) k_reg_normal_eq(ReadingView L, RelPose P, const float* __restrict__ pts, const u32* __restrict__ sample_idx,

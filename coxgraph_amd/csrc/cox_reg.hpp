@@ -1,6 +1,6 @@
 // The per-point value rule of the submap registration, shared by the registration cost (cox_reg.hip) and the pose-candidate sweep
-// (cox_align.hip): the relative pose reading<-reference, the transform of a reference point into the reading layer and the
-// trilinear distance there.  One copy: both units produce the same bits for pos, has and val.
+// (cox_align.hip): the relative pose reading<-reference and the transform of a reference point into the reading layer.  The
+// cell and the trilinear distance there are cox_interp.hpp's.  One copy: both units produce the same bits for pos, has and val.
 #pragma once
 #include <cmath>
 
@@ -36,32 +36,18 @@ static inline RelPose make_rel_pose(const double ref[4], const double read[4]) {
 
 namespace cox {
 
-// The reference point (px, py, pz) in the reading layer under R, t and the 2x2x2 cell around it (voxblox
-// Interpolator<TsdfVoxel>::getVoxelsAndQVector): md = table . corner distances and the offset off inside the cell.  False
-// without a correspondence: the position is not finite or beyond the packed keys, the block of the point or one of the cell is
-// missing, or a corner has weight <= 0.
+// The reference point (px, py, pz) in the reading layer under R, t and the 2x2x2 cell around it there (point_cell of
+// cox_interp.hpp).  False without a correspondence.
 __device__ __forceinline__ bool reg_cell(const LayerView& L, const float* R, const float* t, float px, float py, float pz, float md[8], float off[3]) {
   const float pos[3] = {(R[0] * px + R[1] * py) + R[2] * pz + t[0], (R[3] * px + R[4] * py) + R[5] * pz + t[1], (R[6] * px + R[7] * py) + R[8] * pz + t[2]};
-  float sc[3];
-  if (!block_scaled(L, pos, sc)) return false;
-  int b[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) b[k] = grid_index(sc[k]);
-  if (ht_find(L.ht_keys, L.ht_mask, pack_key(b[0], b[1], b[2])) == kInvalid) return false;  // block of the point must exist
-  float d[8], wv[8];
-  if (!interp_cell(L, pos, b, HtPool{L}, d, wv, off)) return false;
-  interp_table_apply(d, md);
-  return true;
+  return point_cell(L, pos, md, off);
 }
 
 // the interpolated distance of reg_cell's cell: q . md
 __device__ __forceinline__ float reg_value(const float md[8], const float off[3]) {
-  const float dx = off[0], dy = off[1], dz = off[2];
-  const float q[8] = {1.0f, dx, dy, dz, dx * dy, dy * dz, dz * dx, dx * dy * dz};
-  float val = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) val += q[i] * md[i];
-  return val;
+  float q[8];
+  interp_q(off, q);
+  return interp_dot(q, md);
 }
 
 }  // namespace cox

@@ -2,13 +2,13 @@
 //
 //   k_render  one lane per pixel, one wave per 8 x 8 pixel tile (a workgroup is 16 x 16 pixels): neighbouring lanes walk
 //             neighbouring rays, so their voxel loads share cache lines and their block lookups hit the same hash slots.  A ray
-//             is sphere-traced through the layer: a sample is the ADAPTIVE distance of the map queries (trilinear through
-//             interp_cell / interp_member of cox_interp.hpp, else the containing voxel), the next step is |d| * step_scale, an
-//             unallocated block is left through its far face in one step, and a positive sample followed by a non-positive one
+//             is sphere-traced through the layer: a sample is the ADAPTIVE distance of the map queries (tri_sample of
+//             cox_interp.hpp, else its containing_voxel), the next step is |d| * step_scale, an unallocated block
+//             is left through its far face in one step, and a positive sample followed by a non-positive one
 //             is the hit, placed by one linear interpolation.  The blocks around a sample are resolved through a per-lane
-//             cache of the last 2 x 2 x 2 block set (consecutive samples of a ray mostly stay inside it); whatever the cache
-//             does not hold is looked up in the hash table, so the cache never changes an answer.  Lanes do not wait for each
-//             other: a wave ends when its longest ray does.
+//             BlockSet (cox_interp.hpp) of the last 2 x 2 x 2 blocks, moved and filled as the ray asks (consecutive samples
+//             of a ray mostly stay inside it); whatever the cache does not hold is looked up in the hash table, so the cache
+//             never changes an answer.  Lanes do not wait for each other: a wave ends when its longest ray does.
 //
 // Rules and arithmetic: DESIGN.md section 7g.  The float expressions are those of tests/cpp/render_reference.cpp, one by one.
 #include <hip/hip_runtime.h>
@@ -45,101 +45,6 @@ struct RenderParams {
   u32 max_samples;
 };
 
-// Pool indices of the 2 x 2 x 2 blocks from lo on, filled in as the ray asks for them and kept until the ray leaves that set.
-struct RayCache {
-  int lo[3];
-  u32 pool[8];  // (x - lo.x) << 2 | (y - lo.y) << 1 | (z - lo.z); kInvalid when missing
-  u32 have;     // bit c: pool[c] was resolved
-  __device__ __forceinline__ u32 find(const LayerView& L, int x, int y, int z) const {
-    const u32 dx = static_cast<u32>(x - lo[0]), dy = static_cast<u32>(y - lo[1]), dz = static_cast<u32>(z - lo[2]);
-    if (dx <= 1u && dy <= 1u && dz <= 1u) {
-      const u32 sel = (dx << 2) | (dy << 1) | dz;
-      if ((have >> sel) & 1u) {
-        u32 r = pool[0];
-#pragma unroll
-        for (u32 c = 1; c < 8; ++c) r = sel == c ? pool[c] : r;  // no dynamic register indexing (it would go to scratch)
-        return r;
-      }
-    }
-    return HtPool{L}(x, y, z);
-  }
-  // a new corner forgets the set
-  __device__ __forceinline__ void move(const int nlo[3]) {
-    if (nlo[0] != lo[0] || nlo[1] != lo[1] || nlo[2] != lo[2]) {
-      lo[0] = nlo[0], lo[1] = nlo[1], lo[2] = nlo[2];
-      have = 0u;
-    }
-  }
-  // one block of the set (x - lo in 0..1 on every axis): looked up at most once
-  __device__ __forceinline__ u32 own(const LayerView& L, int x, int y, int z) {
-    const u32 sel = (static_cast<u32>(x - lo[0]) << 2) | (static_cast<u32>(y - lo[1]) << 1) | static_cast<u32>(z - lo[2]);
-    if (!((have >> sel) & 1u)) {
-      const u32 p = HtPool{L}(x, y, z);
-#pragma unroll
-      for (u32 c = 0; c < 8; ++c) pool[c] = sel == c ? p : pool[c];
-      have |= 1u << sel;
-    }
-    return find(L, x, y, z);
-  }
-  // the blocks of the set within span (0 or 1 per axis) that are not resolved yet
-  __device__ __forceinline__ void fill(const LayerView& L, const int span[3]) {
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const int mx = (c >> 2) & 1, my = (c >> 1) & 1, mz = c & 1;
-      if (mx <= span[0] && my <= span[1] && mz <= span[2] && !((have >> c) & 1u)) {
-        pool[c] = HtPool{L}(lo[0] + mx, lo[1] + my, lo[2] + mz);
-        have |= 1u << c;
-      }
-    }
-  }
-};
-
-// what interp_cell asks for blocks with
-struct CachedFind {
-  const LayerView& L;
-  const RayCache& cache;
-  __device__ __forceinline__ u32 operator()(int x, int y, int z) const { return cache.find(L, x, y, z); }
-};
-
-// block of p, and the corner / span of the block set that holds the voxels g - r .. g + r around the voxel g containing p
-__device__ __forceinline__ void block_window(const LayerView& L, const float p[3], int r, int b[3], int lo[3], int span[3]) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    b[k] = grid_index(p[k] * L.block_size_inv);
-    const int v = grid_index((p[k] - static_cast<float>(b[k]) * L.block_size) * L.voxel_size_inv);
-    const int g = b[k] * 16 + (v > 15 ? 15 : (v < 0 ? 0 : v));
-    lo[k] = (g - r) >> 4;
-    span[k] = ((g + r) >> 4) - lo[k];
-  }
-}
-
-// Interpolator::getInterpDistance at s: false when the cell is incomplete or invalid
-__device__ __forceinline__ bool tri_sample(const LayerView& L, const CachedFind& bc, const float s[3], float* d) {
-  int b[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) b[k] = grid_index(s[k] * L.block_size_inv);
-  if (bc(b[0], b[1], b[2]) == kInvalid) return false;  // getBlockPtrByCoordinates(pos)
-  float dd[8], ww[8], off[3];
-  if (!interp_cell(L, s, b, bc, dd, ww, off)) return false;
-  *d = interp_member(off, dd);
-  return true;
-}
-
-// Block::getVoxelByCoordinates: the voxel of the containing block (grid index clamped into it), nullptr without the block
-__device__ __forceinline__ const u32* containing_voxel(const LayerView& L, const CachedFind& bc, const float s[3]) {
-  int b[3], v[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) b[k] = grid_index(s[k] * L.block_size_inv);
-  const u32 pool = bc(b[0], b[1], b[2]);
-  if (pool == kInvalid) return nullptr;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int g = grid_index((s[k] - static_cast<float>(b[k]) * L.block_size) * L.voxel_size_inv);
-    v[k] = g > 15 ? 15 : (g < 0 ? 0 : g);
-  }
-  return L.voxels + (static_cast<size_t>(pool) * kVoxelsPerBlock + static_cast<u32>(v[0] + 16 * (v[1] + 16 * v[2]))) * kWordsPerVoxel;
-}
-
 __device__ __forceinline__ F3 rotate(const RenderParams& P, F3 v) { return quat_rotate(P.qw, P.qx, P.qy, P.qz, v); }
 
 __global__ void __launch_bounds__(kRenderThreads) k_render(LayerView L, RenderParams P, float* __restrict__ depth, float* __restrict__ normal,
@@ -158,8 +63,8 @@ __global__ void __launch_bounds__(kRenderThreads) k_render(LayerView L, RenderPa
     const F3 dg = rotate(P, dc);
     const float len = sqrtf(dot3(dc, dc));
     const float o[3] = {P.ox, P.oy, P.oz}, dir[3] = {dg.x, dg.y, dg.z};
-    RayCache cache{{0, 0, 0}, {kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid, kInvalid}, 0u};
-    const CachedFind bc{L, cache};
+    BlockSet cache = kNoBlocks;  // kept from sample to sample until the ray leaves the set
+    const SetFind bc{L, cache};
     float t = P.min_depth, t_prev = 0.0f, d_prev = 0.0f;
     bool have_prev = false;
     while (t <= P.max_depth) {
@@ -193,7 +98,7 @@ __global__ void __launch_bounds__(kRenderThreads) k_render(LayerView L, RenderPa
       }
       cache.fill(L, span);
       float d = 0.0f;
-      bool ok = tri_sample(L, bc, p, &d);
+      bool ok = tri_sample(L, bc, p, &d, nullptr, false);
       if (!ok) {
         const u32* vox = containing_voxel(L, bc, p);
         if (vox != nullptr) {
@@ -243,7 +148,7 @@ __global__ void __launch_bounds__(kRenderThreads) k_render(LayerView L, RenderPa
             const float off = plus ? h : -h;
             const float s[3] = {axis == 0 ? p[0] + off : p[0] + 0.0f, axis == 1 ? p[1] + off : p[1] + 0.0f, axis == 2 ? p[2] + off : p[2] + 0.0f};
             float dv = 0.0f;
-            if (!tri_sample(L, bc, s, &dv)) {
+            if (!tri_sample(L, bc, s, &dv, nullptr, false)) {
               okg = false;
             } else if (!plus) {
               acc = 0.0f + dv * -1.0f;

@@ -38,7 +38,6 @@ using namespace cox;
 namespace {
 
 using TsdfView = cox::LayerView;
-__device__ __forceinline__ u32 find_pool(const TsdfView& L, int bx, int by, int bz) { return HtPool{L}(bx, by, bz); }
 
 // block count + pool indices in (z, y, x) order of the block index (the packed key orders that way)
 int sorted_blocks(cox_layer* L, u32* nb_out, std::vector<u64>* keys_sorted, DevBuf<u32>* d_order) {
@@ -168,7 +167,7 @@ __global__ void __launch_bounds__(256) k_mc_block(TsdfView L, const u32* __restr
   unpack_key(block_keys[pool], &bx, &by, &bz);
   if (threadIdx.x < 8) {
     const int dx = threadIdx.x & 1, dy = (threadIdx.x >> 1) & 1, dz = threadIdx.x >> 2;
-    nbr_pool[threadIdx.x] = (threadIdx.x == 0) ? pool : find_pool(L, bx + dx, by + dy, bz + dz);
+    nbr_pool[threadIdx.x] = (threadIdx.x == 0) ? pool : HtPool{L}(bx + dx, by + dy, bz + dz);
   }
   __syncthreads();
   for (u32 c = threadIdx.x; c < kCorners; c += 256) {
@@ -247,81 +246,10 @@ __global__ void __launch_bounds__(256) k_mc_block(TsdfView L, const u32* __restr
 }
 
 // Interpolator<TsdfVoxel>::getVoxel(pos, &voxel, interpolate = true): interpolated distance and weight, false when one of
-// the 8 neighbours is missing or unobserved
-__constant__ float c_iso_interp_table[8][8] = {{1, 0, 0, 0, 0, 0, 0, 0},   {-1, 0, 0, 0, 1, 0, 0, 0},   {-1, 0, 1, 0, 0, 0, 0, 0},
-                                               {-1, 1, 0, 0, 0, 0, 0, 0},  {1, 0, -1, 0, -1, 0, 1, 0},  {1, -1, -1, 1, 0, 0, 0, 0},
-                                               {1, -1, 0, 0, -1, 1, 0, 0}, {-1, 1, 1, -1, 1, -1, -1, 1}};
-__device__ __forceinline__ float iso_interp_member(const float q[8], const float data[8]) {
-  float md[8];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    float s = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) s += c_iso_interp_table[r][c] * data[c];
-    md[r] = s;
-  }
-  float v = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) v += q[i] * md[i];
-  return v;
-}
+// the 8 neighbours is missing or unobserved.  The shared sampler of cox_interp.hpp, straight on the hash table.
 __device__ __forceinline__ bool interp_distance_weight(const TsdfView& L, const float pos[3], float* d_out, float* w_out) {
   float sc[3];
-  if (!block_scaled(L, pos, sc)) return false;
-  int b[3], vi[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) b[k] = grid_index(sc[k]);
-  if (find_pool(L, b[0], b[1], b[2]) == kInvalid) return false;  // the block of the point itself must exist
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float origin = static_cast<float>(b[k]) * L.block_size;
-    int v = grid_index((pos[k] - origin) * L.voxel_size_inv);
-    v = v > 15 ? 15 : (v < 0 ? 0 : v);
-    const float c = origin + center_coord(v, L.voxel_size);
-    if (pos[k] - c < 0.0f) {
-      v--;
-      if (v < 0) {
-        b[k]--;
-        v += 16;
-      }
-    }
-    vi[k] = v;
-  }
-  const u32 base_pool = find_pool(L, b[0], b[1], b[2]);
-  if (base_pool == kInvalid) return false;
-  float d[8], w[8], off[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float c0 = static_cast<float>(b[k]) * L.block_size + center_coord(vi[k], L.voxel_size);
-    off[k] = (pos[k] - c0) * L.voxel_size_inv;
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    int v[3] = {vi[0] + ((i >> 2) & 1), vi[1] + ((i >> 1) & 1), vi[2] + (i & 1)};
-    int nb[3] = {b[0], b[1], b[2]};
-    bool moved = false;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      if (v[k] >= 16) {
-        nb[k]++;
-        v[k] -= 16;
-        moved = true;
-      }
-    u32 pool = base_pool;
-    if (moved) {
-      pool = find_pool(L, nb[0], nb[1], nb[2]);
-      if (pool == kInvalid) return false;
-    }
-    const u32* vox = L.voxels + (static_cast<size_t>(pool) * kVoxelsPerBlock + static_cast<u32>(v[0] + 16 * (v[1] + 16 * v[2]))) * kWordsPerVoxel;
-    d[i] = __uint_as_float(vox[0]);
-    w[i] = __uint_as_float(vox[1]);
-    if (!(w[i] > 0.0f)) return false;
-  }
-  const float dx = off[0], dy = off[1], dz = off[2];
-  const float q[8] = {1.0f, dx, dy, dz, dx * dy, dy * dz, dz * dx, dx * dy * dz};
-  *d_out = iso_interp_member(q, d);
-  *w_out = iso_interp_member(q, w);
-  return true;
+  return block_scaled(L, pos, sc) && tri_sample(L, HtPool{L}, pos, d_out, w_out, true);
 }
 
 // createConnectedMesh: a vertex whose grid cell (cell size = proximity threshold) already holds an earlier vertex of the mesh
@@ -413,7 +341,7 @@ __global__ void __launch_bounds__(256) k_esdf_neighbors(TsdfView L, const u64* _
   const int dx = static_cast<int>(j % 3u) - 1, dy = static_cast<int>((j / 3u) % 3u) - 1, dz = static_cast<int>(j / 9u) - 1;
   const int x = bx + dx, y = by + dy, z = bz + dz;
   u32 p = kInvalid;
-  if (x >= -kIdxBias && x < kIdxBias && y >= -kIdxBias && y < kIdxBias && z >= -kIdxBias && z < kIdxBias) p = (j == 13u) ? pool : find_pool(L, x, y, z);
+  if (x >= -kIdxBias && x < kIdxBias && y >= -kIdxBias && y < kIdxBias && z >= -kIdxBias && z < kIdxBias) p = (j == 13u) ? pool : HtPool{L}(x, y, z);
   nbr[t] = p;
 }
 // One workgroup per block: the block and a one-voxel halo in LDS, relaxed in place until nothing in the tile moves (values

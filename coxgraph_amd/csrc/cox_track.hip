@@ -3,11 +3,12 @@
 //   k_track_step<DOF>  ONE Gauss-Newton iteration per launch.  256 lanes per workgroup, a fixed number of workgroups walking the
 //                      scan's candidates (every stride-th point) in passes.  A lane moves its point into the layer's frame with the
 //                      integrators' transform, takes the trilinear distance d and its analytic derivative g from one 2x2x2 gather
-//                      (the arithmetic of cox_reg.hip's reg_point), and fills x = sqrt(w) [J(DOF), d, 1, 0...] plus two unscaled
-//                      counters.  Each wave accumulates sum x x^T with v_mfma_f64_16x16x4_f64 exactly as reg_normal_eq_body does;
-//                      workgroup tiles go to a partials array; the workgroup that draws the last ticket sums them in workgroup
-//                      order, and its thread 0 decides (lost / degenerate / converged), solves the damped system by Cholesky and
-//                      writes the next pose, the record and a `done` word.
+//                      (point_cell and interp_value_gradient of cox_interp.hpp, shared with the registration cost), and fills
+//                      x = sqrt(w) [J(DOF), d, 1, 0...] plus two unscaled counters.  sum x x^T is cox_normal_eq.hpp's, shared with
+//                      cox_reg.hip: each wave accumulates with v_mfma_f64_16x16x4_f64, workgroup tiles go to a partials array, the
+//                      workgroup that draws the last ticket sums them in workgroup order.  Its thread 0 decides (lost /
+//                      degenerate / converged), solves the damped system by Cholesky and writes the next pose, the record and a
+//                      `done` word.
 //   cox_track_refine*  max_iterations launches back to back on the tracker's stream, no host round trip: a launch that finds
 //                      `done` set returns at once (a read that is uniform per workgroup, before anything else).  One D2H at the end.
 //   k_track_evaluate   the per-point seam (p_G, d, g, status) through the same device function.
@@ -24,17 +25,16 @@
 #include "../../include/coxgraph_hip_track.h"
 #include "cox_host.hpp"
 #include "cox_interp.hpp"
+#include "cox_normal_eq.hpp"
 
 using namespace cox;
 
 namespace {
 
-constexpr int kTrackThreads = 256;
+constexpr int kTrackThreads = kNeqThreads;
 constexpr u32 kTrackMaxGroups = COX_TRACK_GRID_PASS / kTrackThreads;  // 256: one per CU
-constexpr int kTile = 256;                                            // one 16x16 f64 tile per workgroup
+constexpr int kTile = kNeqTile;                                       // one 16x16 f64 tile per workgroup
 static_assert(kTrackMaxGroups * kTrackThreads == COX_TRACK_GRID_PASS, "the exported grid pass is the launch shape");
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 // the scan: n sensor-frame points, or the n = w * h pixels of a depth image (depth != nullptr) back-projected on the fly
 struct ScanView {
@@ -76,42 +76,19 @@ __device__ __forceinline__ bool scan_point(const ScanView& S, u32 i, F3* p) {
   return isfinite(p->x) && isfinite(p->y) && isfinite(p->z);
 }
 
-// Steps 1 and 3 of the rule for one considered point: p_G, and when the point is used d and g.  The trilinear value and its
-// derivative are reg_point's (cox_reg.hip), expression by expression.
+// Steps 1 and 3 of the rule for one considered point: p_G, and when the point is used d and g.  The cell, the trilinear value
+// and its derivative are the registration cost's: point_cell and interp_value_gradient of cox_interp.hpp.
 __device__ __forceinline__ bool track_point(const LayerView& L, const FrameParams& P, float max_abs_distance, F3 p_C, F3* p_G, float* d_out, F3* g_out) {
   const F3 pg = transform_point(P, p_C);
   *p_G = pg;
   const float pos[3] = {pg.x, pg.y, pg.z};
-  float sc[3];
-  if (!block_scaled(L, pos, sc)) return false;
-  int b[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) b[k] = grid_index(sc[k]);
-  if (ht_find(L.ht_keys, L.ht_mask, pack_key(b[0], b[1], b[2])) == kInvalid) return false;  // block of the point must exist
-  float d[8], wv[8], off[3];
-  if (!interp_cell(L, pos, b, HtPool{L}, d, wv, off)) return false;
-  float md[8];
-  interp_table_apply(d, md);
-  const float dx = off[0], dy = off[1], dz = off[2];
-  const float q[8] = {1.0f, dx, dy, dz, dx * dy, dy * dz, dz * dx, dx * dy * dz};
-  const float qx[8] = {0, 1, 0, 0, dy, 0, dz, dy * dz};
-  const float qy[8] = {0, 0, 1, 0, dx, dz, 0, dz * dx};
-  const float qz[8] = {0, 0, 0, 1, 0, dy, dx, dx * dy};
-  float val = 0.0f, gxf = 0.0f, gyf = 0.0f, gzf = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) val += q[i] * md[i];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    gxf += qx[i] * md[i];
-    gyf += qy[i] * md[i];
-    gzf += qz[i] * md[i];
-  }
-  gxf *= L.voxel_size_inv;
-  gyf *= L.voxel_size_inv;
-  gzf *= L.voxel_size_inv;
+  float md[8], off[3];
+  if (!point_cell(L, pos, md, off)) return false;
+  float val, g[3];
+  interp_value_gradient(md, off, L.voxel_size_inv, &val, g);
   if (max_abs_distance > 0.0f && !(fabsf(val) <= max_abs_distance)) return false;
   *d_out = val;
-  *g_out = F3{gxf, gyf, gzf};
+  *g_out = F3{g[0], g[1], g[2]};
   return true;
 }
 
@@ -254,10 +231,9 @@ template <int DOF>
 __global__ void __launch_bounds__(kTrackThreads) k_track_step(LayerView L, ScanView S, TrackParams C, TrackState* st, double* partials /*[grid][256]*/,
                                                               double* out /*[256]*/, u32* ticket) {
   if (st->done) return;  // the same word for every lane of every workgroup; written by an EARLIER launch only
-  __shared__ double X[kTrackThreads / 64][16][68];  // per wave: 16 components x 64 points (rows padded to 68, as cox_reg.hip)
-  __shared__ double tile[kTrackThreads / 64][kTile];
+  __shared__ double X[kNeqWaves][16][kNeqRow];
+  __shared__ double tile[kNeqWaves][kNeqTile];
   __shared__ double work[64];
-  const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const u32 nb = gridDim.x, bx = blockIdx.x;
   const FrameParams P = pose_params(st->T);
   const double tfx = static_cast<double>(P.tx), tfy = static_cast<double>(P.ty), tfz = static_cast<double>(P.tz);
@@ -267,9 +243,9 @@ __global__ void __launch_bounds__(kTrackThreads) k_track_step(LayerView L, ScanV
   const u32 n_pass = (n_cand + pass - 1) / pass;
   for (u32 it = 0; it < n_pass; ++it) {
     const u32 j = it * pass + bx * kTrackThreads + threadIdx.x;
-    double x[DOF + 4];
+    double x[16];  // components DOF + 4 .. 15 stay zero
 #pragma unroll
-    for (int k = 0; k < DOF + 4; ++k) x[k] = 0.0;
+    for (int k = 0; k < 16; ++k) x[k] = 0.0;
     F3 pc;
     if (j < n_cand && scan_point(S, j * S.stride, &pc)) {
       x[DOF + 3] = 1.0;  // considered
@@ -297,47 +273,10 @@ __global__ void __launch_bounds__(kTrackThreads) k_track_step(LayerView L, ScanV
         x[DOF + 2] = 1.0;  // used
       }
     }
-#pragma unroll
-    for (int k = 0; k < DOF + 4; ++k) X[wave][k][lane] = x[k];
-#pragma unroll
-    for (int k = DOF + 4; k < 16; ++k) X[wave][k][lane] = 0.0;
-    __builtin_amdgcn_wave_barrier();
-    // sum_p x_p x_p^T over this wave's 64 points: 16 MFMA steps of K = 4 points each.
-    // f64 16x16x4 operand map: lane l supplies A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15].
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const double a = X[wave][lane & 15u][4 * t + (lane >> 4)];
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, a, acc, 0, 0, 0);
-    }
-    __builtin_amdgcn_wave_barrier();
+    normal_eq_wave_step(X, x, acc);
   }
-  // f64 C/D map: col = lane & 15, row = (lane >> 4) + 4 * reg
-#pragma unroll
-  for (int r = 0; r < 4; ++r) tile[wave][((lane >> 4) + 4 * r) * 16 + (lane & 15u)] = acc[r];
-  __syncthreads();
-  partials[static_cast<size_t>(bx) * kTile + threadIdx.x] = ((tile[0][threadIdx.x] + tile[1][threadIdx.x]) + tile[2][threadIdx.x]) + tile[3][threadIdx.x];
-  // the workgroup that finishes last sums the partials of all workgroups in workgroup order: same bits every run
-  __shared__ u32 last;
-  __threadfence();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const u32 t = atomicAdd(ticket, 1u);
-    last = (t == nb - 1u) ? 1u : 0u;
-    if (last) *ticket = 0u;  // ready for the next launch on this stream
-  }
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;  // four independent chains; the order of the additions stays fixed
-  u32 bq = 0;
-  for (; bq + 4 <= nb; bq += 4) {
-    s0 += __builtin_nontemporal_load(&partials[static_cast<size_t>(bq) * kTile + threadIdx.x]);
-    s1 += __builtin_nontemporal_load(&partials[static_cast<size_t>(bq + 1) * kTile + threadIdx.x]);
-    s2 += __builtin_nontemporal_load(&partials[static_cast<size_t>(bq + 2) * kTile + threadIdx.x]);
-    s3 += __builtin_nontemporal_load(&partials[static_cast<size_t>(bq + 3) * kTile + threadIdx.x]);
-  }
-  for (; bq < nb; ++bq) s0 += __builtin_nontemporal_load(&partials[static_cast<size_t>(bq) * kTile + threadIdx.x]);
-  const double total = (s0 + s1) + (s2 + s3);
+  double total;
+  if (!normal_eq_finish(tile, acc, partials, ticket, bx, nb, &total)) return;
   out[threadIdx.x] = total;
   tile[0][threadIdx.x] = total;
   __syncthreads();

@@ -71,20 +71,12 @@ __device__ __forceinline__ F3 rotate(const float q[4], F3 v) { return quat_rotat
 
 __device__ __forceinline__ bool coord_in_range(const LayerView& L, float p) { return index_in_range(p * L.block_size_inv); }  // false for NaN, +-inf
 
-// block and voxel of one coordinate: the containing voxel of the NEAREST query (block_window of cox_render.hip)
-__device__ __forceinline__ void locate(const LayerView& L, float p, int* b, int* v) {
-  const int bb = grid_index(p * L.block_size_inv);
-  const int vv = grid_index((p - static_cast<float>(bb) * L.block_size) * L.voxel_size_inv);
-  *b = bb;
-  *v = vv > 15 ? 15 : (vv < 0 ? 0 : vv);
-}
-
 __device__ __forceinline__ bool block_in_range(int b) { return b >= -kIdxBias && b < kIdxBias; }
 
 // rule 3 for voxel v of pool block `pool` (kInvalid: unallocated); the weight too when the block exists
 __device__ __forceinline__ u32 voxel_state(const LayerView& L, const GainParams& P, u32 pool, int vx, int vy, int vz, float* weight) {
   if (pool == kInvalid) return S_UNKNOWN;
-  const u32* vox = L.voxels + (static_cast<size_t>(pool) * kVoxelsPerBlock + static_cast<u32>(vx + 16 * (vy + 16 * vz))) * kWordsPerVoxel;
+  const u32* vox = voxel_ptr(L, pool, vx, vy, vz);
   const float d = __uint_as_float(vox[0]), w = __uint_as_float(vox[1]);
   *weight = w;
   if (!(w > P.min_weight)) return S_UNKNOWN;
