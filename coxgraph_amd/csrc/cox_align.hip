@@ -154,39 +154,19 @@ struct cox_align {
   const cox_regpoints* ref = nullptr;
   const cox_layer* reading = nullptr;
   cox_align_config cfg{};
-  hipStream_t stream = nullptr;
-  u32* d_stored = nullptr;  // cox_align_set_samples
-  u64 stored_cap = 0, stored_samples = 0;
+  Stream stream;
+  DevBuf<u32> d_stored;  // cox_align_set_samples
+  u64 stored_samples = 0;
   bool has_stored = false;
-  AlignPose* d_poses = nullptr;
-  u64 poses_cap = 0;
-  AlignPose* h_poses = nullptr;  // pinned
-  u64 h_poses_cap = 0;
-  cox_align_score* d_rec = nullptr;
-  u64 rec_cap = 0;
-  cox_align_score* h_rec = nullptr;  // pinned
-  u64 h_rec_cap = 0;
-  double* d_part = nullptr;  // cost_part of a pass, then w_part
-  u64 part_cap = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevBuf<AlignPose> d_poses;
+  PinnedBuf<AlignPose> h_poses;
+  DevBuf<cox_align_score> d_rec;
+  PinnedBuf<cox_align_score> h_rec;
+  DevBuf<double> d_part;  // cost_part of a pass, then w_part
+  EventPair ev;
   double ms = 0.0;
   uint64_t sweeps = 0;
 };
-
-template <class T>
-static int pinned_grow(T** p, u64* cap, u64 need) {
-  if (need <= *cap) return COX_OK;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const int st = cox_hip_status(hipHostMalloc(reinterpret_cast<void**>(p), sizeof(T) * need, hipHostMallocDefault));
-  if (st != COX_OK) {
-    *p = nullptr;
-    return st;
-  }
-  *cap = need;
-  return COX_OK;
-}
 
 static bool tau_ok(float tau) { return std::isfinite(tau) && tau > 0.0f; }
 
@@ -201,24 +181,24 @@ static int sweep_once(cox_align* G, const double pose_read[4], const double* pos
   const u32 n_chunks = std::min<u32>(kAlignMaxChunks, (m + kAlignThreads - 1) / kAlignThreads);
   const u64 pass_cap = std::min<u64>(kAlignPartCap / n_chunks, static_cast<u64>(kAlignMaxTiles) * kAlignTile);
   const u64 P = std::min<u64>(M, pass_cap);
-  COX_TRY(pinned_grow(&G->h_poses, &G->h_poses_cap, M));
-  COX_TRY(pinned_grow(&G->h_rec, &G->h_rec_cap, M));
-  COX_TRY(dev_grow(&G->d_poses, &G->poses_cap, M));
-  COX_TRY(dev_grow(&G->d_rec, &G->rec_cap, M));
-  COX_TRY(dev_grow(&G->d_part, &G->part_cap, P * n_chunks + n_chunks));
+  COX_TRY(G->h_poses.grow(M));
+  COX_TRY(G->h_rec.grow(M));
+  COX_TRY(G->d_poses.grow(M));
+  COX_TRY(G->d_rec.grow(M));
+  COX_TRY(G->d_part.grow(P * n_chunks + n_chunks));
   for (u64 c = 0; c < M; ++c) {
     const RelPose R = make_rel_pose(poses_ref + 4 * c, pose_read);
-    for (int k = 0; k < 9; ++k) G->h_poses[c].R[k] = R.R[k];
-    for (int k = 0; k < 3; ++k) G->h_poses[c].t[k] = R.t[k];
+    for (int k = 0; k < 9; ++k) G->h_poses.p[c].R[k] = R.R[k];
+    for (int k = 0; k < 3; ++k) G->h_poses.p[c].t[k] = R.t[k];
   }
   const float inv = 1024.0f / tau;
   hipStream_t s = G->stream;
   cox_layer_wait_writes(G->reading, s);  // frames still in flight on the reading layer
   COX_HIP(hipMemcpyAsync(G->d_poses, G->h_poses, sizeof(AlignPose) * M, hipMemcpyHostToDevice, s));
-  COX_HIP(hipEventRecord(G->ev0, s));
+  COX_HIP(G->ev.begin(s));
   COX_HIP(hipMemsetAsync(G->d_rec, 0, sizeof(cox_align_score) * M, s));
   const LayerView L = layer_view(G->reading);
-  const u32* d_idx = G->has_stored ? G->d_stored : nullptr;
+  const u32* d_idx = G->has_stored ? G->d_stored.p : nullptr;
   double* w_part = G->d_part + P * n_chunks;
   for (u64 base = 0; base < M; base += P) {
     const u32 n = static_cast<u32>(std::min<u64>(P, M - base));
@@ -226,13 +206,13 @@ static int sweep_once(cox_align* G, const double pose_read[4], const double* pos
                        inv, G->cfg.no_correspondence_cost, G->d_rec + base, G->d_part, w_part);
     hipLaunchKernelGGL(k_align_finish, dim3((n + kAlignWaves - 1) / kAlignWaves), dim3(kAlignThreads), 0, s, G->d_rec + base, G->d_part, w_part, n_chunks, m, n);
   }
-  COX_HIP(hipEventRecord(G->ev1, s));
+  COX_HIP(G->ev.end(s));
   COX_HIP(hipMemcpyAsync(G->h_rec, G->d_rec, sizeof(cox_align_score) * M, hipMemcpyDeviceToHost, s));
   COX_HIP(hipStreamSynchronize(s));
   COX_HIP(hipGetLastError());
   std::memcpy(out, G->h_rec, sizeof(cox_align_score) * M);
-  float ms = 0.0f;
-  if (hipEventElapsedTime(&ms, G->ev0, G->ev1) == hipSuccess) {
+  double ms = 0.0;
+  if (G->ev.elapsed_ms(&ms)) {
     G->ms += ms;
     G->sweeps += 1;
   }
@@ -310,10 +290,7 @@ int cox_align_create(const cox_regpoints_t* reference, const cox_layer_t* readin
   G->ref = reference;
   G->reading = L;
   G->cfg = c;
-  bool ok = hipStreamCreateWithFlags(&G->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipEventCreate(&G->ev0) == hipSuccess && hipEventCreate(&G->ev1) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
+  if (G->stream.create() != COX_OK || G->ev.create() != COX_OK) {
     cox_align_destroy(G);
     return COX_ERR_NO_DEVICE;
   }
@@ -325,15 +302,6 @@ void cox_align_destroy(cox_align_t* G) {
   if (!G) return;
   (void)hipSetDevice(G->reading->device);
   if (G->stream) (void)hipStreamSynchronize(G->stream);
-  dev_free(&G->d_stored);
-  dev_free(&G->d_poses);
-  dev_free(&G->d_rec);
-  dev_free(&G->d_part);
-  if (G->h_poses) (void)hipHostFree(G->h_poses);
-  if (G->h_rec) (void)hipHostFree(G->h_rec);
-  if (G->ev0) (void)hipEventDestroy(G->ev0);
-  if (G->ev1) (void)hipEventDestroy(G->ev1);
-  if (G->stream) (void)hipStreamDestroy(G->stream);
   delete G;
 }
 
@@ -348,7 +316,7 @@ int cox_align_set_samples(cox_align_t* G, const uint32_t* sample_idx, uint64_t m
   G->has_stored = false;
   G->stored_samples = 0;
   if (!sample_idx) return COX_OK;  // back to "all points in order"
-  COX_TRY(dev_grow(&G->d_stored, &G->stored_cap, std::max<uint64_t>(m, 1)));
+  COX_TRY(G->d_stored.grow(std::max<uint64_t>(m, 1)));
   if (m) COX_HIP(hipMemcpy(G->d_stored, sample_idx, sizeof(u32) * m, hipMemcpyHostToDevice));
   G->has_stored = true;
   G->stored_samples = m;

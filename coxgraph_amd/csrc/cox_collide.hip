@@ -344,15 +344,13 @@ struct cox_collide {
   CollideParams P;
   int group = 32;
   bool profiling = false, timing_pending = false;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  ull* d_stats = nullptr;  // evaluated, skipped
+  Stream stream;
+  EventPair ev;
+  DevBuf<ull> d_stats;  // evaluated, skipped
   u64 n_launches = 0;
   double kernel_ms = 0.0;
-  u32* d_words = nullptr;  // pointer-jumping buffers, 2 x n
-  u64 words_cap = 0;
-  uint8_t* d_stage = nullptr;  // staging of the host entry points
-  u64 stage_cap = 0;
+  DevBuf<u32> d_words;      // pointer-jumping buffers, 2 x n
+  DevBuf<uint8_t> d_stage;  // staging of the host entry points
 };
 
 namespace {
@@ -361,11 +359,11 @@ namespace {
 void settle_timing(cox_collide* H) {
   if (!H->timing_pending) return;
   H->timing_pending = false;
-  float ms = 0.0f;
-  if (hipEventSynchronize(H->ev1) == hipSuccess && hipEventElapsedTime(&ms, H->ev0, H->ev1) == hipSuccess)
-    H->kernel_ms += static_cast<double>(ms);
-  else
+  double ms = 0.0;
+  if (hipEventSynchronize(H->ev.b) != hipSuccess)
     (void)hipGetLastError();
+  else if (H->ev.elapsed_ms(&ms))
+    H->kernel_ms += ms;
 }
 struct Timed {
   cox_collide* H;
@@ -373,12 +371,12 @@ struct Timed {
   Timed(cox_collide* h, hipStream_t st) : H(h), s(st) {
     if (H->profiling) {
       settle_timing(H);
-      (void)hipEventRecord(H->ev0, s);
+      (void)H->ev.begin(s);
     }
   }
   ~Timed() {
     if (H->profiling) {
-      (void)hipEventRecord(H->ev1, s);
+      (void)H->ev.end(s);
       H->timing_pending = true;
     }
   }
@@ -388,7 +386,7 @@ u32 blocks_for(u64 items, u64 per_block) { return static_cast<u32>((items + per_
 
 int enqueue_points(cox_collide* H, const float* xyz, u64 n, uint8_t* state, float* distance, hipStream_t s) {
   hipLaunchKernelGGL(k_collide_points, dim3(blocks_for(n, kThreads)), dim3(kThreads), 0, s, layer_view(H->layer), H->P, xyz, n, state, distance,
-                     H->d_stats);
+                     H->d_stats.p);
   H->n_launches++;
   COX_HIP(hipGetLastError());
   return COX_OK;
@@ -397,9 +395,9 @@ int enqueue_points(cox_collide* H, const float* xyz, u64 n, uint8_t* state, floa
 int enqueue_segments(cox_collide* H, const float* a, const float* b, u64 n, cox_collide_record* out, hipStream_t s) {
   const LayerView V = layer_view(H->layer);  // read on every call: a layer that grew has new buffers
   if (H->group == 64)
-    hipLaunchKernelGGL((k_collide_segments<64>), dim3(blocks_for(n, kThreads / 64)), dim3(kThreads), 0, s, V, H->P, a, b, n, out, H->d_stats);
+    hipLaunchKernelGGL((k_collide_segments<64>), dim3(blocks_for(n, kThreads / 64)), dim3(kThreads), 0, s, V, H->P, a, b, n, out, H->d_stats.p);
   else
-    hipLaunchKernelGGL((k_collide_segments<32>), dim3(blocks_for(n, kThreads / 32)), dim3(kThreads), 0, s, V, H->P, a, b, n, out, H->d_stats);
+    hipLaunchKernelGGL((k_collide_segments<32>), dim3(blocks_for(n, kThreads / 32)), dim3(kThreads), 0, s, V, H->P, a, b, n, out, H->d_stats.p);
   H->n_launches++;
   COX_HIP(hipGetLastError());
   return COX_OK;
@@ -409,10 +407,10 @@ int enqueue_trajectories(cox_collide* H, const u64* offsets, u64 n_traj, const f
   const LayerView V = layer_view(H->layer);
   if (H->group == 64)
     hipLaunchKernelGGL((k_collide_trajectories<64>), dim3(blocks_for(n_traj, kThreads / 64)), dim3(kThreads), 0, s, V, H->P, offsets, n_traj, xyz,
-                       n_points, out, H->d_stats);
+                       n_points, out, H->d_stats.p);
   else
     hipLaunchKernelGGL((k_collide_trajectories<32>), dim3(blocks_for(n_traj, kThreads / 32)), dim3(kThreads), 0, s, V, H->P, offsets, n_traj, xyz,
-                       n_points, out, H->d_stats);
+                       n_points, out, H->d_stats.p);
   H->n_launches++;
   COX_HIP(hipGetLastError());
   return COX_OK;
@@ -425,9 +423,9 @@ int enqueue_prune(cox_collide* H, const int32_t* parent, const uint8_t* feasible
     hipLaunchKernelGGL(k_prune_small, dim3(1), dim3(kPruneThreads), 0, s, parent, feasible, stride, n, rounds, keep);
     H->n_launches++;
   } else {
-    COX_TRY(dev_grow(&H->d_words, &H->words_cap, 2 * n64));
-    u32* w0 = H->d_words;
-    u32* w1 = H->d_words + n64;
+    COX_TRY(H->d_words.grow(2 * n64));
+    u32* w0 = H->d_words.p;
+    u32* w1 = H->d_words.p + n64;
     const dim3 grid(blocks_for(n64, kThreads));
     hipLaunchKernelGGL(k_prune_init, grid, dim3(kThreads), 0, s, parent, feasible, stride, n, w0);
     for (int r = 0; r < rounds; ++r) {
@@ -450,6 +448,13 @@ int begin_call(cox_collide* H, hipStream_t s) {
   COX_HIP(hipSetDevice(H->layer->device));
   cox_layer_wait_writes(H->layer, s);  // frames still in flight on the layer
   return COX_OK;
+}
+
+int collide_resources(cox_collide* H) {
+  COX_TRY(H->stream.create());
+  COX_TRY(H->ev.create());
+  COX_TRY(H->d_stats.alloc(2));
+  return cox_hip_status(hipMemset(H->d_stats.p, 0, 2 * sizeof(ull)));
 }
 
 }  // namespace
@@ -492,12 +497,7 @@ int cox_collide_create(cox_layer_t* layer, const cox_collide_config* cfg, cox_co
   P.max_ext = c.max_extension_range, P.crop_margin = c.crop_margin, P.crop_min_length = c.crop_min_length;
   P.max_samples = c.max_samples ? c.max_samples : kDefaultMaxSamples;
   P.optimistic = c.collision_optimistic != 0, P.crop = c.crop != 0;
-  bool ok = hipStreamCreateWithFlags(&H->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipEventCreate(&H->ev0) == hipSuccess && hipEventCreate(&H->ev1) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&H->d_stats), 2 * sizeof(ull)) == hipSuccess;
-  ok = ok && hipMemset(H->d_stats, 0, 2 * sizeof(ull)) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
+  if (collide_resources(H) != COX_OK) {
     cox_collide_destroy(H);
     return COX_ERR_NO_DEVICE;
   }
@@ -509,12 +509,6 @@ void cox_collide_destroy(cox_collide_t* H) {
   if (!H) return;
   (void)hipSetDevice(H->layer->device);
   if (H->stream) (void)hipStreamSynchronize(H->stream);
-  void* ptrs[] = {H->d_stats, H->d_words, H->d_stage};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (H->ev0) (void)hipEventDestroy(H->ev0);
-  if (H->ev1) (void)hipEventDestroy(H->ev1);
-  if (H->stream) (void)hipStreamDestroy(H->stream);
   delete H;
 }
 
@@ -550,13 +544,13 @@ int cox_collide_stats(cox_collide_t* H, cox_collide_stats_t* out, int reset) {
   COX_HIP(hipSetDevice(H->layer->device));
   settle_timing(H);
   ull c[2] = {0, 0};
-  COX_HIP(hipMemcpy(c, H->d_stats, sizeof(c), hipMemcpyDeviceToHost));
+  COX_HIP(hipMemcpy(c, H->d_stats.p, sizeof(c), hipMemcpyDeviceToHost));
   out->n_samples_evaluated = c[0];
   out->n_samples_skipped = c[1];
   out->n_launches = H->n_launches;
   out->kernel_ms = H->kernel_ms;
   if (reset) {
-    COX_HIP(hipMemset(H->d_stats, 0, sizeof(c)));
+    COX_HIP(hipMemset(H->d_stats.p, 0, sizeof(c)));
     H->n_launches = 0;
     H->kernel_ms = 0.0;
   }
@@ -574,10 +568,10 @@ int cox_collide_points(cox_collide_t* H, const float* xyz, uint64_t n, uint8_t* 
   COX_TRY(begin_call(H, s));
   // staging: xyz | distance | state
   const u64 b_xyz = 12 * n, b_d = distance ? 4 * n : 0, b_s = state ? n : 0;
-  COX_TRY(dev_grow(&H->d_stage, &H->stage_cap, b_xyz + b_d + b_s));
-  float* d_xyz = reinterpret_cast<float*>(H->d_stage);
-  float* d_d = distance ? reinterpret_cast<float*>(H->d_stage + b_xyz) : nullptr;
-  uint8_t* d_s = state ? H->d_stage + b_xyz + b_d : nullptr;
+  COX_TRY(H->d_stage.grow(b_xyz + b_d + b_s));
+  float* d_xyz = reinterpret_cast<float*>(H->d_stage.p);
+  float* d_d = distance ? reinterpret_cast<float*>(H->d_stage.p + b_xyz) : nullptr;
+  uint8_t* d_s = state ? H->d_stage.p + b_xyz + b_d : nullptr;
   COX_HIP(hipMemcpyAsync(d_xyz, xyz, b_xyz, hipMemcpyHostToDevice, s));
   if (d_d) COX_HIP(hipMemsetAsync(d_d, 0xFF, b_d, s));  // NaN where nothing is written
   {
@@ -614,10 +608,10 @@ int cox_collide_segments(cox_collide_t* H, const float* a, const float* b, uint6
   COX_TRY(begin_call(H, s));
   // staging: records | a | b
   const u64 b_rec = sizeof(cox_collide_record) * n, b_pts = 12 * n;
-  COX_TRY(dev_grow(&H->d_stage, &H->stage_cap, b_rec + 2 * b_pts));
-  cox_collide_record* d_rec = reinterpret_cast<cox_collide_record*>(H->d_stage);
-  float* d_a = reinterpret_cast<float*>(H->d_stage + b_rec);
-  float* d_b = reinterpret_cast<float*>(H->d_stage + b_rec + b_pts);
+  COX_TRY(H->d_stage.grow(b_rec + 2 * b_pts));
+  cox_collide_record* d_rec = reinterpret_cast<cox_collide_record*>(H->d_stage.p);
+  float* d_a = reinterpret_cast<float*>(H->d_stage.p + b_rec);
+  float* d_b = reinterpret_cast<float*>(H->d_stage.p + b_rec + b_pts);
   COX_HIP(hipMemcpyAsync(d_a, a, b_pts, hipMemcpyHostToDevice, s));
   COX_HIP(hipMemcpyAsync(d_b, b, b_pts, hipMemcpyHostToDevice, s));
   {
@@ -663,8 +657,8 @@ int host_trajectories(cox_collide* H, const uint64_t* offsets, const int32_t* pa
   COX_TRY(begin_call(H, s));
   // staging: records | offsets | xyz | parent | keep
   const u64 b_rec = sizeof(cox_collide_record) * n, b_off = 8 * (n + 1), b_xyz = 12 * n_points, b_par = parent ? 4 * n : 0, b_keep = keep ? n : 0;
-  COX_TRY(dev_grow(&H->d_stage, &H->stage_cap, b_rec + b_off + b_xyz + b_par + b_keep));
-  uint8_t* base = H->d_stage;
+  COX_TRY(H->d_stage.grow(b_rec + b_off + b_xyz + b_par + b_keep));
+  uint8_t* base = H->d_stage.p;
   cox_collide_record* d_rec = reinterpret_cast<cox_collide_record*>(base);
   u64* d_off = reinterpret_cast<u64*>(base + b_rec);
   float* d_xyz = reinterpret_cast<float*>(base + b_rec + b_off);

@@ -58,10 +58,9 @@ RcclApi& rccl() {
 struct cox_comm {
   int device = 0, rank = 0, world = 1;
   ncclComm_t comm = nullptr;
-  hipStream_t stream = nullptr;
-  double* d_buf = nullptr;
-  uint64_t cap = 0;
-  hipEvent_t ev = nullptr;  // producer stream -> collective stream
+  Stream stream;
+  DevBuf<double> d_buf;
+  Event ev;  // producer stream -> collective stream
 };
 
 #define COX_NCCL(call)                                                                                                                 \
@@ -99,18 +98,17 @@ int cox_comm_init_rank(int device, int rank, int world, const uint8_t id[COX_COM
   C->world = world;
   ncclUniqueId u;
   memcpy(u.internal, id, COX_COMM_ID_BYTES);
-  if (hipStreamCreateWithFlags(&C->stream, hipStreamNonBlocking) != hipSuccess) {
+  if (C->stream.create() != COX_OK) {
     delete C;
     return COX_ERR_NO_DEVICE;
   }
   const ncclResult_t r = rccl().CommInitRank(&C->comm, world, u, rank);
   if (r != ncclSuccess) {
     fprintf(stderr, "[coxgraph_hip] ncclCommInitRank -> %s\n", rccl().GetErrorString ? rccl().GetErrorString(r) : "?");
-    (void)hipStreamDestroy(C->stream);
     delete C;
     return COX_ERR_COMM;
   }
-  if (hipEventCreateWithFlags(&C->ev, hipEventDisableTiming) != hipSuccess) C->ev = nullptr;
+  (void)C->ev.create(false);  // without it the collectives wait for the producer on the host
   *out = C;
   return COX_OK;
 }
@@ -120,9 +118,6 @@ void cox_comm_destroy(cox_comm_t* C) {
   (void)hipSetDevice(C->device);
   if (C->stream) (void)hipStreamSynchronize(C->stream);
   if (C->comm && rccl().ok) (void)rccl().CommDestroy(C->comm);
-  if (C->d_buf) (void)hipFree(C->d_buf);
-  if (C->ev) (void)hipEventDestroy(C->ev);
-  if (C->stream) (void)hipStreamDestroy(C->stream);
   delete C;
 }
 
@@ -138,15 +133,9 @@ int cox_comm_allreduce_f64(cox_comm_t* C, double* buf, uint64_t n) {
   if (!C || (n && !buf)) return COX_ERR_INVALID_ARG;
   if (n == 0) return COX_OK;
   COX_HIP(hipSetDevice(C->device));
-  if (n > C->cap) {
-    if (C->d_buf) (void)hipFree(C->d_buf);
-    C->d_buf = nullptr;
-    C->cap = 0;
-    COX_HIP(hipMalloc(reinterpret_cast<void**>(&C->d_buf), sizeof(double) * n));
-    C->cap = n;
-  }
+  COX_TRY(C->d_buf.grow(n));
   COX_HIP(hipMemcpyAsync(C->d_buf, buf, sizeof(double) * n, hipMemcpyHostToDevice, C->stream));
-  COX_NCCL(rccl().AllReduce(C->d_buf, C->d_buf, n, ncclFloat64, ncclSum, C->comm, C->stream));
+  COX_NCCL(rccl().AllReduce(C->d_buf.p, C->d_buf.p, n, ncclFloat64, ncclSum, C->comm, C->stream));
   COX_HIP(hipMemcpyAsync(buf, C->d_buf, sizeof(double) * n, hipMemcpyDeviceToHost, C->stream));
   COX_HIP(hipStreamSynchronize(C->stream));
   return COX_OK;

@@ -367,18 +367,26 @@ struct cox_depthfuse {
   int device = 0;
   cox_layer* layer = nullptr;
   cox_depthfuse_config cfg{};
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_in = nullptr, ev_read = nullptr;  // the producer's work so far; the frame has read its images
-  hipEvent_t ev_t[4] = {nullptr, nullptr, nullptr, nullptr};  // selection begin / end, update begin / end
-  u32* d_ctl = nullptr;  // kHostWords
-  u32* h_ctl = nullptr;  // pinned, kHostWords
+  Stream stream;
+  Event ev_in, ev_read;  // the producer's work so far; the frame has read its images
+  Event ev_t[4];         // selection begin / end, update begin / end
+  DevBuf<u32> d_ctl;     // kHostWords
+  PinnedBuf<u32> h_ctl;  // kHostWords
   // per candidate, sized by the largest frame so far
   u64 cand_cap = 0;
-  u32 *d_touched = nullptr, *d_scan_t = nullptr, *d_new = nullptr, *d_pool_of = nullptr, *d_list = nullptr, *d_sums = nullptr;
+  DevBuf<u32> d_touched, d_scan_t, d_new, d_pool_of, d_list, d_sums;
   // staging of host images
-  float* d_depth = nullptr;
-  uint8_t* d_rgba = nullptr;
-  u64 depth_cap = 0, rgba_cap = 0;  // floats, bytes
+  DevBuf<float> d_depth;
+  DevBuf<uint8_t> d_rgba;
+
+  int acquire() {
+    COX_TRY(stream.create());
+    COX_TRY(ev_in.create(false));
+    COX_TRY(ev_read.create(false));
+    for (Event& e : ev_t) COX_TRY(e.create(true));
+    COX_TRY(d_ctl.alloc(kHostWords));
+    return h_ctl.alloc(kHostWords);
+  }
   cox_depthfuse_stats last{};
   bool pending = false;   // the last frame's counters are still on the device
   bool timed[2] = {false, false};
@@ -389,20 +397,15 @@ namespace {
 int grow_candidates(cox_depthfuse* H, u64 n) {
   if (n <= H->cand_cap) return COX_OK;
   COX_HIP(hipStreamSynchronize(H->stream));
-  for (u32** q : {&H->d_touched, &H->d_scan_t, &H->d_new, &H->d_pool_of, &H->d_list, &H->d_sums}) {
-    if (*q) (void)hipFree(*q);
-    *q = nullptr;
-  }
+  DevBuf<u32>* const per_candidate[] = {&H->d_touched, &H->d_scan_t, &H->d_new, &H->d_pool_of, &H->d_list};
+  for (DevBuf<u32>* q : per_candidate) q->reset();
+  H->d_sums.reset();
   H->cand_cap = 0;
   const u64 cap = std::min<u64>(std::max<u64>(n, 4096), COX_DEPTHFUSE_MAX_CANDIDATES);
   bool ok = true;
-  for (u32** q : {&H->d_touched, &H->d_scan_t, &H->d_new, &H->d_pool_of, &H->d_list})
-    ok = ok && hipMalloc(reinterpret_cast<void**>(q), sizeof(u32) * cap) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&H->d_sums), sizeof(u32) * (scan_num_blocks(static_cast<u32>(cap)) + 1)) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    return COX_ERR_OUT_OF_MEMORY;
-  }
+  for (DevBuf<u32>* q : per_candidate) ok = ok && q->alloc(cap) == COX_OK;
+  ok = ok && H->d_sums.alloc(scan_num_blocks(static_cast<u32>(cap)) + 1) == COX_OK;
+  if (!ok) return COX_ERR_OUT_OF_MEMORY;
   H->cand_cap = cap;
   return COX_OK;
 }
@@ -499,10 +502,10 @@ int frame(cox_depthfuse* H, const Box& box, const float T[7], const float* depth
   // the frame's single host read
   COX_HIP(hipMemcpyAsync(H->h_ctl, H->d_ctl, sizeof(u32) * kHostWords, hipMemcpyDeviceToHost, s));
   COX_HIP(hipStreamSynchronize(s));
-  if (H->h_ctl[kHostErr]) return err_bits_to_status(H->h_ctl[kHostErr]);  // no frame onto a layer in error
-  const u32 n_touched = H->h_ctl[kCtlTouched], n_new = H->h_ctl[kCtlNew];
+  if (H->h_ctl.p[kHostErr]) return err_bits_to_status(H->h_ctl.p[kHostErr]);  // no frame onto a layer in error
+  const u32 n_touched = H->h_ctl.p[kCtlTouched], n_new = H->h_ctl.p[kCtlNew];
   if (n_touched > n_cand || n_new > n_touched) return COX_ERR_INTERNAL;
-  const u32 nb0 = static_cast<u32>(std::min<u64>(H->h_ctl[kHostNb], L->capacity));
+  const u32 nb0 = static_cast<u32>(std::min<u64>(H->h_ctl.p[kHostNb], L->capacity));
   const u64 nb1 = static_cast<u64>(nb0) + n_new;
   if (nb1 > L->capacity) {
     if (!L->auto_grow) return COX_ERR_POOL_EXHAUSTED;  // nothing was written
@@ -593,14 +596,7 @@ int cox_depthfuse_create(cox_layer_t* layer, const cox_depthfuse_config* cfg_in,
   H->layer = layer;
   H->device = layer->device;
   H->cfg = cfg;
-  bool ok = hipStreamCreateWithFlags(&H->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&H->ev_in, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&H->ev_read, hipEventDisableTiming) == hipSuccess;
-  for (hipEvent_t& e : H->ev_t) ok = ok && hipEventCreate(&e) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&H->d_ctl), sizeof(u32) * kHostWords) == hipSuccess;
-  ok = ok && hipHostMalloc(reinterpret_cast<void**>(&H->h_ctl), sizeof(u32) * kHostWords, hipHostMallocDefault) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
+  if (H->acquire() != COX_OK) {
     cox_depthfuse_destroy(H);
     return COX_ERR_NO_DEVICE;
   }
@@ -613,14 +609,6 @@ void cox_depthfuse_destroy(cox_depthfuse_t* H) {
   if (!H) return;
   (void)hipSetDevice(H->device);
   if (H->stream) (void)hipStreamSynchronize(H->stream);  // nothing of this integrator is in flight after this
-  for (u32* q : {H->d_ctl, H->d_touched, H->d_scan_t, H->d_new, H->d_pool_of, H->d_list, H->d_sums})
-    if (q) (void)hipFree(q);
-  if (H->d_depth) (void)hipFree(H->d_depth);
-  if (H->d_rgba) (void)hipFree(H->d_rgba);
-  if (H->h_ctl) (void)hipHostFree(H->h_ctl);
-  for (hipEvent_t e : {H->ev_in, H->ev_read, H->ev_t[0], H->ev_t[1], H->ev_t[2], H->ev_t[3]})
-    if (e) (void)hipEventDestroy(e);
-  if (H->stream) (void)hipStreamDestroy(H->stream);
   delete H;
 }
 
@@ -653,11 +641,11 @@ int cox_depthfuse_integrate(cox_depthfuse_t* H, const float T[7], const float* d
   COX_HIP(hipSetDevice(H->device));
   const size_t n_px = static_cast<size_t>(w) * static_cast<size_t>(height);
   COX_HIP(hipStreamSynchronize(H->stream));  // the staging buffers are single: the frame that read them last is done
-  COX_TRY(dev_grow(&H->d_depth, &H->depth_cap, n_px));
-  if (rgba) COX_TRY(dev_grow(&H->d_rgba, &H->rgba_cap, 4 * n_px));
+  COX_TRY(H->d_depth.grow(n_px));
+  if (rgba) COX_TRY(H->d_rgba.grow(4 * n_px));
   COX_HIP(hipMemcpyAsync(H->d_depth, depth, sizeof(float) * n_px, hipMemcpyHostToDevice, H->stream));
   if (rgba) COX_HIP(hipMemcpyAsync(H->d_rgba, rgba, 4 * n_px, hipMemcpyHostToDevice, H->stream));
-  return frame(H, box, T, H->d_depth, rgba ? H->d_rgba : nullptr, w, height, K);
+  return frame(H, box, T, H->d_depth, rgba ? H->d_rgba.p : nullptr, w, height, K);
 }
 
 int cox_depthfuse_sync(cox_depthfuse_t* H) {
@@ -668,7 +656,7 @@ int cox_depthfuse_sync(cox_depthfuse_t* H) {
   u32 err = 0;
   COX_HIP(hipMemcpyAsync(H->h_ctl + kHostErr, H->layer->d_err, sizeof(u32), hipMemcpyDeviceToHost, H->stream));
   COX_HIP(hipStreamSynchronize(H->stream));
-  err = H->h_ctl[kHostErr];
+  err = H->h_ctl.p[kHostErr];
   return err_bits_to_status(err);
 }
 

@@ -260,18 +260,18 @@ struct cox_esdf {
   cox_layer* E = nullptr;
   int device = 0;      // the TSDF's; kept here so that destroying the handle never reads the TSDF
   cox_esdf_config cfg{};
-  hipStream_t stream = nullptr;
+  Stream stream;
   bool valid = false;  // E mirrors the first nb pool blocks of the TSDF and is the fixed point of what the last update saw
   u32 nb = 0;          // blocks mirrored
   u32 hi = 0;          // pool blocks of E that may hold anything but zeros
   u32 frame_id = 0;    // the TSDF's frame counter at the last update (cox_layer_clear takes it back to zero)
   u64 cap = 0;         // blocks the arrays below are sized for (E's capacity)
-  u32* d_nbr = nullptr;       // [cap][27]
-  u32* d_act[2] = {nullptr, nullptr};
-  u32* d_touched = nullptr;   // classify or raise changed the block in this update
-  u32* d_swept = nullptr;
-  u32* d_ctl = nullptr;       // kCtlWords
-  u32* h_ctl = nullptr;       // pinned, kHostWords
+  DevBuf<u32> d_nbr;  // [cap][27]
+  DevBuf<u32> d_act[2];
+  DevBuf<u32> d_touched;  // classify or raise changed the block in this update
+  DevBuf<u32> d_swept;
+  DevBuf<u32> d_ctl;     // kCtlWords
+  PinnedBuf<u32> h_ctl;  // kHostWords
 };
 
 namespace {
@@ -279,22 +279,12 @@ namespace {
 int grow_arrays(cox_esdf* H) {
   const u64 cap = H->E->capacity;
   if (cap <= H->cap && H->d_nbr) return COX_OK;
-  u32 *nbr = nullptr, *a0 = nullptr, *a1 = nullptr, *touched = nullptr, *swept = nullptr;
-  bool ok = hipMalloc(reinterpret_cast<void**>(&nbr), sizeof(u32) * 27 * cap) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&a0), sizeof(u32) * cap) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&a1), sizeof(u32) * cap) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&touched), sizeof(u32) * cap) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&swept), sizeof(u32) * cap) == hipSuccess;
-  if (ok && H->d_nbr && H->nb) ok = hipMemcpy(nbr, H->d_nbr, sizeof(u32) * 27 * H->nb, hipMemcpyDeviceToDevice) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    for (u32* q : {nbr, a0, a1, touched, swept})
-      if (q) (void)hipFree(q);
-    return COX_ERR_OUT_OF_MEMORY;
-  }
-  for (u32* q : {H->d_nbr, H->d_act[0], H->d_act[1], H->d_touched, H->d_swept})
-    if (q) (void)hipFree(q);
-  H->d_nbr = nbr, H->d_act[0] = a0, H->d_act[1] = a1, H->d_touched = touched, H->d_swept = swept;
+  // the new set; after the swaps these hold the old one, which goes with them
+  DevBuf<u32> nbr, a0, a1, touched, swept;
+  bool ok = nbr.alloc(27 * cap) == COX_OK && a0.alloc(cap) == COX_OK && a1.alloc(cap) == COX_OK && touched.alloc(cap) == COX_OK && swept.alloc(cap) == COX_OK;
+  if (ok && H->d_nbr && H->nb) ok = cox_hip_status(hipMemcpy(nbr, H->d_nbr, sizeof(u32) * 27 * H->nb, hipMemcpyDeviceToDevice)) == COX_OK;
+  if (!ok) return COX_ERR_OUT_OF_MEMORY;
+  H->d_nbr.swap(nbr), H->d_act[0].swap(a0), H->d_act[1].swap(a1), H->d_touched.swap(touched), H->d_swept.swap(swept);
   H->cap = cap;
   return COX_OK;
 }
@@ -330,8 +320,8 @@ int run_phase(cox_esdf* H, u32 nb, uint64_t* n_sweeps) {
     COX_HIP(hipGetLastError());
     COX_TRY(read_ctl(H));
     for (int k = 0; k < kSweepsPerRead; ++k) {
-      if (H->h_ctl[kCtlSweepActive + k]) *n_sweeps += 1;
-      if (H->h_ctl[kCtlSweepChanged + k] == 0) return COX_OK;  // nothing moved: nothing is active after it
+      if (H->h_ctl.p[kCtlSweepActive + k]) *n_sweeps += 1;
+      if (H->h_ctl.p[kCtlSweepChanged + k] == 0) return COX_OK;  // nothing moved: nothing is active after it
     }
   }
   return COX_ERR_INTERNAL;
@@ -354,9 +344,9 @@ int update_impl(cox_esdf* H, cox_esdf_update_stats* st) {
   COX_HIP(hipMemcpyAsync(H->h_ctl + kHostNb, T->d_nblocks, sizeof(u32), hipMemcpyDeviceToHost, s));
   COX_HIP(hipMemcpyAsync(H->h_ctl + kHostErr, T->d_err, sizeof(u32), hipMemcpyDeviceToHost, s));
   COX_TRY(read_ctl(H));
-  if (H->h_ctl[kHostErr]) return err_bits_to_status(H->h_ctl[kHostErr]);  // as cox_esdf_from_tsdf: no ESDF of a layer in error
-  const u32 nb = static_cast<u32>(std::min<u64>(H->h_ctl[kHostNb], T->capacity));
-  const bool rebuild = !was_valid || nb < H->nb || H->h_ctl[kCtlMismatch] != 0 || T->frame_id < H->frame_id;
+  if (H->h_ctl.p[kHostErr]) return err_bits_to_status(H->h_ctl.p[kHostErr]);  // as cox_esdf_from_tsdf: no ESDF of a layer in error
+  const u32 nb = static_cast<u32>(std::min<u64>(H->h_ctl.p[kHostNb], T->capacity));
+  const bool rebuild = !was_valid || nb < H->nb || H->h_ctl.p[kCtlMismatch] != 0 || T->frame_id < H->frame_id;
   H->frame_id = T->frame_id;
   if (rebuild) {
     COX_HIP(hipMemsetAsync(E->ht_keys, 0xFF, sizeof(u64) * E->ht_cap, s));
@@ -399,7 +389,7 @@ int update_impl(cox_esdf* H, cox_esdf_update_stats* st) {
                      H->d_touched, H->d_ctl);
   COX_HIP(hipGetLastError());
   COX_TRY(read_ctl(H));
-  st->n_dirty_blocks = H->h_ctl[kCtlDirty];
+  st->n_dirty_blocks = H->h_ctl.p[kCtlDirty];
   if (st->n_dirty_blocks) {
     // 3. raise (an ESDF that started empty holds init values only: nothing to raise), then 4. lower
     if (!rebuild) COX_TRY(run_phase<true>(H, nb, &st->n_raise_sweeps));
@@ -409,11 +399,11 @@ int update_impl(cox_esdf* H, cox_esdf_update_stats* st) {
   memcpy(v64, H->h_ctl + kCtlReset, sizeof(v64));  // reset, changed
   st->n_reset_voxels = v64[0];
   st->n_changed_voxels = v64[1];
-  st->n_swept_blocks = H->h_ctl[kCtlSwept];
+  st->n_swept_blocks = H->h_ctl.p[kCtlSwept];
   u32 err = 0;
   COX_HIP(hipMemcpyAsync(H->h_ctl + kHostErr, E->d_err, sizeof(u32), hipMemcpyDeviceToHost, s));
   COX_HIP(hipStreamSynchronize(s));
-  err = H->h_ctl[kHostErr];
+  err = H->h_ctl.p[kHostErr];
   if (err) return err_bits_to_status(err);
   H->valid = true;
   return COX_OK;
@@ -442,13 +432,7 @@ int cox_esdf_create(cox_layer_t* tsdf, const cox_esdf_config* cfg_in, cox_esdf_t
   int st = cox_layer_create(tsdf->voxel_size, kVps, tsdf->device, 64, &H->E);
   if (st == COX_OK) st = grow_arrays(H);
   if (st == COX_OK) {
-    bool ok = hipStreamCreateWithFlags(&H->stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&H->d_ctl), sizeof(u32) * kCtlWords) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&H->h_ctl), sizeof(u32) * kHostWords, hipHostMallocDefault) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      st = COX_ERR_NO_DEVICE;
-    }
+    if (H->stream.create() != COX_OK || H->d_ctl.alloc(kCtlWords) != COX_OK || H->h_ctl.alloc(kHostWords) != COX_OK) st = COX_ERR_NO_DEVICE;
   }
   if (st != COX_OK) {
     cox_esdf_destroy(H);
@@ -463,10 +447,6 @@ void cox_esdf_destroy(cox_esdf_t* H) {
   if (!H) return;
   (void)hipSetDevice(H->device);
   if (H->stream) (void)hipStreamSynchronize(H->stream);
-  for (u32* q : {H->d_nbr, H->d_act[0], H->d_act[1], H->d_touched, H->d_swept, H->d_ctl})
-    if (q) (void)hipFree(q);
-  if (H->h_ctl) (void)hipHostFree(H->h_ctl);
-  if (H->stream) (void)hipStreamDestroy(H->stream);
   if (H->E) cox_layer_destroy(H->E);
   delete H;
 }

@@ -51,16 +51,16 @@ struct cox_obs {
   float voxel_size = 0, voxel_size_inv = 0;
   u64 capacity = 0;
   u32 ht_cap = 0;
-  u64* ht_keys = nullptr;
-  u32* ht_vals = nullptr;
-  u32* masks = nullptr;
-  u64* block_keys = nullptr;
-  u32* ctl = nullptr;
-  u32* shard = nullptr;
-  u32* h_ctl = nullptr;  // pinned: ctl as the last record left it (the host sees the pool fill up without a sync)
-  hipStream_t st = nullptr;
-  hipEvent_t ev_count = nullptr;  // h_ctl of the last record has landed
-  hipEvent_t ev_caller = nullptr, ev_read = nullptr;  // cox_obs_record_dev: the caller's stream so far / the cloud has been read
+  DevBuf<u64> ht_keys;
+  DevBuf<u32> ht_vals;
+  DevBuf<u32> masks;
+  DevBuf<u64> block_keys;
+  DevBuf<u32> ctl;
+  DevBuf<u32> shard;
+  PinnedBuf<u32> h_ctl;  // ctl as the last record left it (the host sees the pool fill up without a sync)
+  Stream st;
+  Event ev_count;            // h_ctl of the last record has landed
+  Event ev_caller, ev_read;  // cox_obs_record_dev: the caller's stream so far / the cloud has been read
   bool has_record = false;
   u32 frame_id = 0;
   bool auto_grow = true;
@@ -255,44 +255,34 @@ ObsView obs_view(const cox_obs* O) {
   return ObsView{O->ht_keys, O->ht_vals, O->ht_cap - 1, O->masks, O->block_keys, static_cast<u32>(O->capacity), O->ctl, O->shard};
 }
 
-void obs_free_pool(cox_obs* O) {
-  for (void* p : {static_cast<void*>(O->ht_keys), static_cast<void*>(O->ht_vals), static_cast<void*>(O->masks), static_cast<void*>(O->block_keys)})
-    if (p) (void)hipFree(p);
-  O->ht_keys = nullptr, O->ht_vals = nullptr, O->masks = nullptr, O->block_keys = nullptr;
-}
-
 // table + pool of `capacity` blocks, empty, on the record's stream
-int obs_alloc_pool(u64 capacity, u64** ht_keys, u32** ht_vals, u32** masks, u64** block_keys, u32* ht_cap, hipStream_t s) {
+int obs_alloc_pool(u64 capacity, DevBuf<u64>* ht_keys, DevBuf<u32>* ht_vals, DevBuf<u32>* masks, DevBuf<u64>* block_keys, u32* ht_cap, hipStream_t s) {
   *ht_cap = next_pow2(2 * capacity);
-  COX_TRY(dev_alloc(ht_keys, *ht_cap));
-  COX_TRY(dev_alloc(ht_vals, *ht_cap));
-  COX_TRY(dev_alloc(masks, capacity * kObsBlockWords));
-  COX_TRY(dev_alloc(block_keys, capacity));
-  COX_HIP(hipMemsetAsync(*ht_keys, 0xFF, sizeof(u64) * *ht_cap, s));
-  COX_HIP(hipMemsetAsync(*ht_vals, 0xFF, sizeof(u32) * *ht_cap, s));
-  COX_HIP(hipMemsetAsync(*masks, 0, sizeof(u32) * capacity * kObsBlockWords, s));  // bump-allocated blocks start out unmarked
+  COX_TRY(ht_keys->alloc(*ht_cap));
+  COX_TRY(ht_vals->alloc(*ht_cap));
+  COX_TRY(masks->alloc(capacity * kObsBlockWords));
+  COX_TRY(block_keys->alloc(capacity));
+  COX_HIP(hipMemsetAsync(ht_keys->p, 0xFF, sizeof(u64) * *ht_cap, s));
+  COX_HIP(hipMemsetAsync(ht_vals->p, 0xFF, sizeof(u32) * *ht_cap, s));
+  COX_HIP(hipMemsetAsync(masks->p, 0, sizeof(u32) * capacity * kObsBlockWords, s));  // bump-allocated blocks start out unmarked
   return COX_OK;
 }
 
 // stream idle: the pool with `capacity` blocks, the marks kept
 int obs_reserve(cox_obs* O, u64 capacity) {
-  u64 *keys = nullptr, *bkeys = nullptr;
-  u32 *vals = nullptr, *masks = nullptr, ht_cap = 0;
-  const int st = obs_alloc_pool(capacity, &keys, &vals, &masks, &bkeys, &ht_cap, O->st);
-  if (st != COX_OK) {
-    for (void* p : {static_cast<void*>(keys), static_cast<void*>(vals), static_cast<void*>(masks), static_cast<void*>(bkeys)})
-      if (p) (void)hipFree(p);
-    return st;
-  }
-  const u32 n = static_cast<u32>(std::min<u64>(O->h_ctl[kCtlBlocks], O->capacity));
+  // the new pool; after the swaps these hold the old one, which goes with them
+  DevBuf<u64> keys, bkeys;
+  DevBuf<u32> vals, masks;
+  u32 ht_cap = 0;
+  COX_TRY(obs_alloc_pool(capacity, &keys, &vals, &masks, &bkeys, &ht_cap, O->st));
+  const u32 n = static_cast<u32>(std::min<u64>(O->h_ctl.p[kCtlBlocks], O->capacity));
   if (n) {
     COX_HIP(hipMemcpyAsync(masks, O->masks, sizeof(u32) * kObsBlockWords * n, hipMemcpyDeviceToDevice, O->st));
     COX_HIP(hipMemcpyAsync(bkeys, O->block_keys, sizeof(u64) * n, hipMemcpyDeviceToDevice, O->st));
-    hipLaunchKernelGGL(k_obs_rehash, dim3((n + 255) / 256), dim3(256), 0, O->st, keys, vals, ht_cap - 1, bkeys, n, O->ctl);
+    hipLaunchKernelGGL(k_obs_rehash, dim3((n + 255) / 256), dim3(256), 0, O->st, keys.p, vals.p, ht_cap - 1, bkeys.p, n, O->ctl.p);
   }
   COX_HIP(hipStreamSynchronize(O->st));
-  obs_free_pool(O);
-  O->ht_keys = keys, O->ht_vals = vals, O->masks = masks, O->block_keys = bkeys;
+  O->ht_keys.swap(keys), O->ht_vals.swap(vals), O->masks.swap(masks), O->block_keys.swap(bkeys);
   O->ht_cap = ht_cap;
   O->capacity = capacity;
   return COX_OK;
@@ -301,7 +291,7 @@ int obs_reserve(cox_obs* O, u64 capacity) {
 // The pool doubles once it is half full -- or will be, at the largest rate seen between two looks (the host's view of the count is
 // as old as the records still in flight).  A cloud that outruns it all the same loses marks and says so (kErrPool).
 int obs_follow(cox_obs* O) {
-  const u64 n_seen = O->h_ctl[kCtlBlocks];
+  const u64 n_seen = O->h_ctl.p[kCtlBlocks];
   if (n_seen > O->blocks_seen) O->blocks_delta_max = std::max<u64>(O->blocks_delta_max, n_seen - O->blocks_seen);
   O->blocks_seen = n_seen;
   const u64 need = std::max<u64>(2 * n_seen, n_seen + 8 * O->blocks_delta_max);
@@ -323,7 +313,7 @@ int obs_settle(cox_obs* O, bool take_errors) {
   COX_HIP(hipStreamSynchronize(O->st));
   u32 h[kCtlWords] = {0, 0};
   COX_HIP(hipMemcpy(h, O->ctl, sizeof(h), hipMemcpyDeviceToHost));
-  O->h_ctl[kCtlBlocks] = h[kCtlBlocks];
+  O->h_ctl.p[kCtlBlocks] = h[kCtlBlocks];
   if (!take_errors || h[kCtlErr] == 0) return COX_OK;
   COX_HIP(hipMemsetAsync(O->ctl + kCtlErr, 0, sizeof(u32), O->st));
   COX_HIP(hipStreamSynchronize(O->st));
@@ -334,13 +324,6 @@ void obs_free(cox_obs* O) {
   if (!O) return;
   (void)hipSetDevice(O->device);
   if (O->st) (void)hipStreamSynchronize(O->st);
-  obs_free_pool(O);
-  if (O->ctl) (void)hipFree(O->ctl);
-  if (O->shard) (void)hipFree(O->shard);
-  if (O->h_ctl) (void)hipHostFree(O->h_ctl);
-  for (hipEvent_t e : {O->ev_count, O->ev_caller, O->ev_read})
-    if (e) (void)hipEventDestroy(e);
-  if (O->st) (void)hipStreamDestroy(O->st);
   delete O;
   (void)hipGetLastError();
 }
@@ -356,22 +339,17 @@ int tri_history(const cox_meshlayer* M, cox_obs* O, TriHistory* H, u32 n_tri, u3
   COX_TRY(H->off.alloc(n_tri));
   COX_TRY(H->total.alloc(1));
   COX_TRY(H->sums.alloc(scan_num_blocks(n_tri) + 2));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (kernel_ms && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) return COX_ERR_NO_DEVICE;
-  if (e0) (void)hipEventRecord(e0, O->st);
+  EventPair ev;
+  if (kernel_ms && ev.create() != COX_OK) return COX_ERR_NO_DEVICE;
+  if (kernel_ms) (void)ev.begin(O->st);
   hipLaunchKernelGGL(k_tri_mask, dim3((n_tri + 255) / 256), dim3(256), 0, O->st, M->pos, n_tri, O->voxel_size_inv, O->ht_keys, O->ht_vals, O->ht_cap - 1, O->masks,
                      static_cast<u32>(O->capacity), H->mask.p, H->words.p);
   const ScanWorkspace ws{H->sums.p};
   exclusive_scan_u32(H->words.p, H->off.p, nullptr, n_tri, n_tri, H->total.p, ws, O->st);
-  if (e1) (void)hipEventRecord(e1, O->st);
+  if (kernel_ms) (void)ev.end(O->st);
   COX_HIP(hipMemcpyAsync(n_words, H->total.p, sizeof(u32), hipMemcpyDeviceToHost, O->st));
   COX_HIP(hipStreamSynchronize(O->st));
-  if (e0 && e1) {
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *kernel_ms = ms;
-  }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
+  if (kernel_ms && !ev.elapsed_ms(kernel_ms)) return COX_ERR_NO_DEVICE;
   COX_HIP(hipGetLastError());
   return COX_OK;
 }
@@ -440,13 +418,13 @@ int cox_obs_create(const cox_layer_t* L, uint64_t capacity_blocks, cox_obs_t** o
     obs_free(O);
     return st;
   };
-  bool ok = hipStreamCreateWithFlags(&O->st, hipStreamNonBlocking) == hipSuccess;
-  for (hipEvent_t* e : {&O->ev_count, &O->ev_caller, &O->ev_read}) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipHostMalloc(reinterpret_cast<void**>(&O->h_ctl), sizeof(u32) * kCtlWords, hipHostMallocDefault) == hipSuccess;
+  bool ok = O->st.create() == COX_OK;
+  for (Event* e : {&O->ev_count, &O->ev_caller, &O->ev_read}) ok = ok && e->create(false) == COX_OK;
+  ok = ok && O->h_ctl.alloc(kCtlWords) == COX_OK;
   if (!ok) return fail(COX_ERR_NO_DEVICE);
-  O->h_ctl[kCtlBlocks] = O->h_ctl[kCtlErr] = 0;
-  if (int st = dev_alloc(&O->ctl, kCtlWords)) return fail(st);
-  if (int st = dev_alloc(&O->shard, 128)) return fail(st);
+  O->h_ctl.p[kCtlBlocks] = O->h_ctl.p[kCtlErr] = 0;
+  if (int st = O->ctl.alloc(kCtlWords)) return fail(st);
+  if (int st = O->shard.alloc(128)) return fail(st);
   if (int st = obs_alloc_pool(O->capacity, &O->ht_keys, &O->ht_vals, &O->masks, &O->block_keys, &O->ht_cap, O->st)) return fail(st);
   if (hipMemsetAsync(O->ctl, 0, sizeof(u32) * kCtlWords, O->st) != hipSuccess || hipMemsetAsync(O->shard, 0, sizeof(u32) * 128, O->st) != hipSuccess ||
       hipStreamSynchronize(O->st) != hipSuccess)
@@ -469,7 +447,7 @@ int cox_obs_clear(cox_obs_t* O) {
   COX_HIP(hipMemsetAsync(O->ctl, 0, sizeof(u32) * kCtlWords, O->st));
   COX_HIP(hipMemsetAsync(O->shard, 0, sizeof(u32) * 128, O->st));
   COX_HIP(hipStreamSynchronize(O->st));
-  O->h_ctl[kCtlBlocks] = O->h_ctl[kCtlErr] = 0;
+  O->h_ctl.p[kCtlBlocks] = O->h_ctl.p[kCtlErr] = 0;
   O->blocks_seen = O->blocks_delta_max = 0;
   return COX_OK;
 }
@@ -515,14 +493,14 @@ int cox_obs_record(cox_obs_t* O, const float T_G_C[7], const float* xyz, uint64_
     COX_HIP(hipStreamSynchronize(O->st));
     // This call waits for its cloud anyway, so it loses nothing to a full pool: double the pool and mark the cloud again (marking is
     // idempotent; the rebuilt table drops the blocks that found no room).
-    if (!(O->h_ctl[kCtlErr] & (kErrPool | kErrTable)) || !O->auto_grow || O->capacity >= kObsMaxCapacity) break;
+    if (!(O->h_ctl.p[kCtlErr] & (kErrPool | kErrTable)) || !O->auto_grow || O->capacity >= kObsMaxCapacity) break;
     const int st = obs_reserve(O, std::min<u64>(2 * O->capacity, kObsMaxCapacity));
     if (st == COX_ERR_OUT_OF_MEMORY) {
       O->auto_grow = false;
       break;
     }
     COX_TRY(st);
-    const u32 keep = O->h_ctl[kCtlErr] & ~(kErrPool | kErrTable);
+    const u32 keep = O->h_ctl.p[kCtlErr] & ~(kErrPool | kErrTable);
     COX_HIP(hipMemcpyAsync(O->ctl + kCtlErr, &keep, sizeof(u32), hipMemcpyHostToDevice, O->st));
     COX_HIP(hipStreamSynchronize(O->st));
   }
@@ -539,7 +517,7 @@ int cox_obs_stats(cox_obs_t* O, uint64_t* n_blocks, uint64_t* n_marked_cells, ui
   COX_ENTRY();
   if (!O) return COX_ERR_INVALID_ARG;
   COX_TRY(obs_settle(O, false));
-  const u32 nb = static_cast<u32>(std::min<u64>(O->h_ctl[kCtlBlocks], O->capacity));
+  const u32 nb = static_cast<u32>(std::min<u64>(O->h_ctl.p[kCtlBlocks], O->capacity));
   if (n_blocks) *n_blocks = nb;
   if (bytes)
     *bytes = O->capacity * (sizeof(u32) * kObsBlockWords + sizeof(u64)) + static_cast<u64>(O->ht_cap) * (sizeof(u64) + sizeof(u32)) + sizeof(u32) * (kCtlWords + 128);
@@ -576,7 +554,7 @@ int cox_obs_download(cox_obs_t* O, int32_t* block_index, uint32_t* masks, uint64
   COX_ENTRY();
   if (!O || !n_blocks) return COX_ERR_INVALID_ARG;
   COX_TRY(obs_settle(O, false));
-  const u32 nb = static_cast<u32>(std::min<u64>(O->h_ctl[kCtlBlocks], O->capacity));
+  const u32 nb = static_cast<u32>(std::min<u64>(O->h_ctl.p[kCtlBlocks], O->capacity));
   *n_blocks = nb;
   if (!block_index && !masks) return COX_OK;
   if (cap_blocks < nb) return COX_ERR_BUFFER_TOO_SMALL;

@@ -1758,13 +1758,12 @@ int cox_selftest_division(int device, uint64_t n, uint64_t seed, uint64_t* misma
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return COX_ERR_NO_DEVICE;
   COX_HIP(hipSetDevice(device));
-  u32* d = nullptr;
-  COX_HIP(hipMalloc(reinterpret_cast<void**>(&d), sizeof(u32)));
+  DevBuf<u32> d;
+  COX_TRY(d.alloc(1));
   COX_HIP(hipMemset(d, 0, sizeof(u32)));
-  hipLaunchKernelGGL(k_selftest_division, dim3(4096), dim3(256), 0, nullptr, n, seed, d);
+  hipLaunchKernelGGL(k_selftest_division, dim3(4096), dim3(256), 0, nullptr, n, seed, d.p);
   u32 h = 0;
   COX_HIP(hipMemcpy(&h, d, sizeof(u32), hipMemcpyDeviceToHost));
-  (void)hipFree(d);
   *mismatches = h;
   return COX_OK;
 }
@@ -1780,30 +1779,27 @@ int cox_selftest_scan_small(int device, const uint32_t* in_a, const uint32_t* in
   COX_HIP(hipSetDevice(device));
   // one allocation: in_a, in_b, four outputs, the count, four totals
   const size_t words = std::max<size_t>(len, 1);
-  u32* d = nullptr;
-  COX_HIP(hipMalloc(reinterpret_cast<void**>(&d), (6 * words + 5) * sizeof(u32)));
+  DevBuf<u32> buf;
+  COX_TRY(buf.alloc(6 * words + 5));
+  u32* d = buf.p;
   u32 *d_in[2] = {d, d + words}, *d_out = d + 2 * words, *d_cnt = d + 6 * words, *d_tot = d_cnt + 1;
-  const int st = [&]() -> int {
-    if (len) {
-      COX_HIP(hipMemcpy(d_in[0], in_a, len * sizeof(u32), hipMemcpyHostToDevice));
-      COX_HIP(hipMemcpy(d_in[1], in_b, len * sizeof(u32), hipMemcpyHostToDevice));
-    }
-    COX_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d_out), static_cast<int>(sentinel), 4 * words));
-    COX_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d_tot), static_cast<int>(sentinel), 4));
-    COX_HIP(hipMemcpy(d_cnt, &d_n, sizeof(u32), hipMemcpyHostToDevice));
-    COX_HIP(hipDeviceSynchronize());
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, nullptr, d_in[0], d_out, d_cnt, n_max, d_tot);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, nullptr, d_in[1], d_out + words, d_cnt, n_max, d_tot + 1);
-    hipLaunchKernelGGL(k_scan_small2, dim3(1), dim3(1024), 0, nullptr, d_in[0], d_out + 2 * words, d_tot + 2, d_in[1], d_out + 3 * words, d_tot + 3, d_cnt, n_max);
-    COX_HIP(hipGetLastError());
-    COX_HIP(hipDeviceSynchronize());
-    uint32_t* outs[4] = {out1_a, out1_b, out2_a, out2_b};
-    for (int k = 0; k < 4 && len; ++k) COX_HIP(hipMemcpy(outs[k], d_out + k * words, len * sizeof(u32), hipMemcpyDeviceToHost));
-    COX_HIP(hipMemcpy(totals, d_tot, 4 * sizeof(u32), hipMemcpyDeviceToHost));
-    return COX_OK;
-  }();
-  (void)hipFree(d);
-  return st;
+  if (len) {
+    COX_HIP(hipMemcpy(d_in[0], in_a, len * sizeof(u32), hipMemcpyHostToDevice));
+    COX_HIP(hipMemcpy(d_in[1], in_b, len * sizeof(u32), hipMemcpyHostToDevice));
+  }
+  COX_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d_out), static_cast<int>(sentinel), 4 * words));
+  COX_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d_tot), static_cast<int>(sentinel), 4));
+  COX_HIP(hipMemcpy(d_cnt, &d_n, sizeof(u32), hipMemcpyHostToDevice));
+  COX_HIP(hipDeviceSynchronize());
+  hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, nullptr, d_in[0], d_out, d_cnt, n_max, d_tot);
+  hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, nullptr, d_in[1], d_out + words, d_cnt, n_max, d_tot + 1);
+  hipLaunchKernelGGL(k_scan_small2, dim3(1), dim3(1024), 0, nullptr, d_in[0], d_out + 2 * words, d_tot + 2, d_in[1], d_out + 3 * words, d_tot + 3, d_cnt, n_max);
+  COX_HIP(hipGetLastError());
+  COX_HIP(hipDeviceSynchronize());
+  uint32_t* outs[4] = {out1_a, out1_b, out2_a, out2_b};
+  for (int k = 0; k < 4 && len; ++k) COX_HIP(hipMemcpy(outs[k], d_out + k * words, len * sizeof(u32), hipMemcpyDeviceToHost));
+  COX_HIP(hipMemcpy(totals, d_tot, 4 * sizeof(u32), hipMemcpyDeviceToHost));
+  return COX_OK;
 }
 
 // words of a 64-word guard on the device that no longer hold the sentinel
@@ -1864,37 +1860,34 @@ int cox_selftest_copy_from_host(int device, const uint32_t* a, uint64_t words_a,
   // both sides: a, then b from the next multiple of 16 bytes on; on the device a guard behind each
   const size_t G = kSelftestGuard, a4 = (words_a + 3) & ~static_cast<size_t>(3), b4 = (words_b + 3) & ~static_cast<size_t>(3);
   const size_t o_b = a4 + G, words = o_b + b4 + G;
-  u32* pinned = nullptr;
-  COX_HIP(hipHostMalloc(reinterpret_cast<void**>(&pinned), (a4 + b4 + 4) * sizeof(u32), hipHostMallocDefault));
-  const int st = [&]() -> int {
-    DevBuf<u32> buf;
-    COX_TRY(buf.alloc(words));
-    u32* d = buf.p;
-    if (words_a) memcpy(pinned, a, words_a * sizeof(u32));
-    if (words_b) memcpy(pinned + a4, b, words_b * sizeof(u32));
-    const u32* pinned_dev = static_cast<const u32*>(host_pointer_device_view(pinned));
-    if (!pinned_dev || (reinterpret_cast<uintptr_t>(pinned_dev) & 15u) || (reinterpret_cast<uintptr_t>(d) & 15u)) return COX_ERR_INTERNAL;
-    COX_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d), static_cast<int>(sentinel), words));
-    COX_HIP(hipDeviceSynchronize());
-    const HostSegment A = host_segment(d, pinned_dev, words_a * sizeof(u32));
-    const HostSegment B = b ? host_segment(d + o_b, pinned_dev + a4, words_b * sizeof(u32)) : HostSegment{nullptr, nullptr, 0, 0};
-    hipLaunchKernelGGL(k_copy_from_host, dim3(groups), dim3(256), 0, nullptr, A, B);
-    COX_HIP(hipGetLastError());
-    COX_HIP(hipDeviceSynchronize());
-    // (the padding words between an array's end and its guard count as guard: nothing may write them either)
-    if (words_a) COX_HIP(hipMemcpy(out_a, d, words_a * sizeof(u32), hipMemcpyDeviceToHost));
-    if (words_b) COX_HIP(hipMemcpy(out_b, d + o_b, words_b * sizeof(u32), hipMemcpyDeviceToHost));
-    for (int k = 0; k < 2; ++k) {
-      const size_t end = k ? o_b + words_b : words_a, stop = k ? words : o_b;
-      std::vector<u32> g(stop - end);
-      COX_HIP(hipMemcpy(g.data(), d + end, g.size() * sizeof(u32), hipMemcpyDeviceToHost));
-      guard_touched[k] = 0;
-      for (u32 v : g) guard_touched[k] += v != sentinel ? 1u : 0u;
-    }
-    return COX_OK;
-  }();
-  (void)hipHostFree(pinned);
-  return st;
+  PinnedBuf<u32> host;
+  COX_TRY(host.alloc(a4 + b4 + 4));
+  u32* pinned = host.p;
+  DevBuf<u32> buf;
+  COX_TRY(buf.alloc(words));
+  u32* d = buf.p;
+  if (words_a) memcpy(pinned, a, words_a * sizeof(u32));
+  if (words_b) memcpy(pinned + a4, b, words_b * sizeof(u32));
+  const u32* pinned_dev = static_cast<const u32*>(host_pointer_device_view(pinned));
+  if (!pinned_dev || (reinterpret_cast<uintptr_t>(pinned_dev) & 15u) || (reinterpret_cast<uintptr_t>(d) & 15u)) return COX_ERR_INTERNAL;
+  COX_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d), static_cast<int>(sentinel), words));
+  COX_HIP(hipDeviceSynchronize());
+  const HostSegment A = host_segment(d, pinned_dev, words_a * sizeof(u32));
+  const HostSegment B = b ? host_segment(d + o_b, pinned_dev + a4, words_b * sizeof(u32)) : HostSegment{nullptr, nullptr, 0, 0};
+  hipLaunchKernelGGL(k_copy_from_host, dim3(groups), dim3(256), 0, nullptr, A, B);
+  COX_HIP(hipGetLastError());
+  COX_HIP(hipDeviceSynchronize());
+  // (the padding words between an array's end and its guard count as guard: nothing may write them either)
+  if (words_a) COX_HIP(hipMemcpy(out_a, d, words_a * sizeof(u32), hipMemcpyDeviceToHost));
+  if (words_b) COX_HIP(hipMemcpy(out_b, d + o_b, words_b * sizeof(u32), hipMemcpyDeviceToHost));
+  for (int k = 0; k < 2; ++k) {
+    const size_t end = k ? o_b + words_b : words_a, stop = k ? words : o_b;
+    std::vector<u32> g(stop - end);
+    COX_HIP(hipMemcpy(g.data(), d + end, g.size() * sizeof(u32), hipMemcpyDeviceToHost));
+    guard_touched[k] = 0;
+    for (u32 v : g) guard_touched[k] += v != sentinel ? 1u : 0u;
+  }
+  return COX_OK;
 }
 
 int cox_integrator_stage_times(cox_integrator_t* I, double ms[2], uint64_t launches[2], int reset) {

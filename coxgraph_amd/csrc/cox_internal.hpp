@@ -107,7 +107,13 @@ struct cox_regpoints {
   u64 n = 0;
   u64* cum = nullptr;    // inclusive prefix sums of the fixed-point weights (built on first use by the weighted sampler)
   u64 cum_total = 0;
+  ~cox_regpoints() {  // like the other handles below: whoever deletes one has set its device
+    if (pts) (void)hipFree(pts);
+    if (cum) (void)hipFree(cum);
+  }
 };
+// cox_reg.hip: a set of n points on `device` (the current one), not yet filled; pts stays null for n == 0
+int regpoints_new(int device, u64 n, cox_regpoints** out);
 
 // voxblox::MeshLayer of a TSDF layer (cox_mesher.hip builds it, cox_history.hip reads it)
 struct cox_meshlayer {
@@ -122,6 +128,11 @@ struct cox_meshlayer {
   u64 n_color_missing = 0;
   double kernel_ms[2] = {0.0, 0.0};
   bool transformed = false;          // cox_meshlayer_transform has moved it out of the layer's frame
+  ~cox_meshlayer() {
+    if (pos) (void)hipFree(pos);
+    if (nrm) (void)hipFree(nrm);
+    if (rgb) (void)hipFree(rgb);
+  }
 };
 
 // voxblox::Mesh after createConnectedMesh (cox_mesher.hip builds it, cox_meshclean.hip works on it in place)
@@ -132,6 +143,21 @@ struct cox_meshconn {
   float* nrm = nullptr;    // 3 per vertex
   uint8_t* rgb = nullptr;  // 3 per vertex
   u32* tri = nullptr;      // 3 per triangle
+  // new arrays (or none) in place of the ones held, which are freed
+  void set_vertices(float* p, float* n, uint8_t* c) {
+    if (pos) (void)hipFree(pos);
+    if (nrm) (void)hipFree(nrm);
+    if (rgb) (void)hipFree(rgb);
+    pos = p, nrm = n, rgb = c;
+  }
+  void set_triangles(u32* t) {
+    if (tri) (void)hipFree(tri);
+    tri = t;
+  }
+  ~cox_meshconn() {
+    set_vertices(nullptr, nullptr, nullptr);
+    set_triangles(nullptr);
+  }
 };
 
 // observation record of a submap (cox_history.hip).  An integrator it is attached to hands it every cloud it fuses:

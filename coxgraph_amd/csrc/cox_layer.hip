@@ -50,6 +50,29 @@ static int layer_reset_storage(cox_layer* L, u64 used_blocks, hipStream_t s) {
   return COX_OK;
 }
 
+// The buffers of a layer whose size follows its capacity.  They are allocated here and handed to the layer by exchange(): what the
+// layer held before (nothing, for a new one) is then freed with this object.
+struct LayerStorage {
+  DevBuf<u32> voxels, ht_vals, ht_stamp, ht_ord;
+  DevBuf<u64> ht_keys, block_keys;
+  int alloc(u64 capacity, u32 ht_cap) {
+    COX_TRY(voxels.alloc(capacity * kVoxelsPerBlock * kWordsPerVoxel));
+    COX_TRY(ht_keys.alloc(ht_cap));
+    COX_TRY(ht_vals.alloc(ht_cap));
+    COX_TRY(ht_stamp.alloc(ht_cap));
+    COX_TRY(ht_ord.alloc(ht_cap));
+    return block_keys.alloc(capacity);
+  }
+  void exchange(cox_layer* L) {
+    std::swap(voxels.p, L->voxels);
+    std::swap(ht_keys.p, L->ht_keys);
+    std::swap(ht_vals.p, L->ht_vals);
+    std::swap(ht_stamp.p, L->ht_stamp);
+    std::swap(ht_ord.p, L->ht_ord);
+    std::swap(block_keys.p, L->block_keys);
+  }
+};
+
 static int layer_read_counters(const cox_layer* L, u32* nblocks, u32* err) {
   COX_HIP(hipSetDevice(L->device));
   COX_HIP(hipDeviceSynchronize());
@@ -158,22 +181,20 @@ int cox_layer_create(float voxel_size, int voxels_per_side, int device, uint64_t
   }
   L->ht_cap = next_pow2(2 * L->capacity);
   if (L->ht_cap < 1024) L->ht_cap = 1024;
-  const size_t vox_bytes = L->capacity * kVoxelsPerBlock * kWordsPerVoxel * sizeof(u32);
-  int st = COX_OK;
-  auto alloc = [&](void** p, size_t bytes) {
-    if (st != COX_OK) return;
-    st = cox_hip_status(hipMalloc(p, bytes));
-  };
-  alloc(reinterpret_cast<void**>(&L->voxels), vox_bytes);
-  alloc(reinterpret_cast<void**>(&L->ht_keys), sizeof(u64) * L->ht_cap);
-  alloc(reinterpret_cast<void**>(&L->ht_vals), sizeof(u32) * L->ht_cap);
-  alloc(reinterpret_cast<void**>(&L->ht_stamp), sizeof(u32) * L->ht_cap);
-  alloc(reinterpret_cast<void**>(&L->ht_ord), sizeof(u32) * L->ht_cap);
-  alloc(reinterpret_cast<void**>(&L->block_keys), sizeof(u64) * L->capacity);
-  alloc(reinterpret_cast<void**>(&L->d_nblocks), sizeof(u32));
-  alloc(reinterpret_cast<void**>(&L->d_err), sizeof(u32));
-  if (st == COX_OK && hipHostMalloc(reinterpret_cast<void**>(&L->h_nblocks), sizeof(u32), hipHostMallocDefault) != hipSuccess) st = COX_ERR_OUT_OF_MEMORY;
-  if (st == COX_OK && hipEventCreateWithFlags(&L->last_write, hipEventDisableTiming) != hipSuccess) st = COX_ERR_NO_DEVICE;
+  LayerStorage S;
+  DevBuf<u32> d_nblocks, d_err;
+  PinnedBuf<u32> h_nblocks;
+  Event last_write;
+  int st = S.alloc(L->capacity, L->ht_cap);
+  if (st == COX_OK) st = d_nblocks.alloc(1);
+  if (st == COX_OK) st = d_err.alloc(1);
+  if (st == COX_OK && h_nblocks.alloc(1) != COX_OK) st = COX_ERR_OUT_OF_MEMORY;
+  if (st == COX_OK && last_write.create(false) != COX_OK) st = COX_ERR_NO_DEVICE;
+  S.exchange(L);  // the layer owns its buffers from here on (cox_layer_destroy)
+  L->d_nblocks = d_nblocks.release();
+  L->d_err = d_err.release();
+  L->h_nblocks = h_nblocks.release();
+  std::swap(L->last_write, last_write.e);
   L->auto_grow = std::getenv("COX_NO_GROW") == nullptr;
   if (st == COX_OK) st = layer_reset_storage(L, L->capacity, nullptr);
   if (st == COX_OK && hipDeviceSynchronize() != hipSuccess) st = COX_ERR_NO_DEVICE;
@@ -197,8 +218,10 @@ void cox_layer_destroy(cox_layer_t* L) {
   (void)hipFree(L->block_keys);
   (void)hipFree(L->d_nblocks);
   (void)hipFree(L->d_err);
-  if (L->h_nblocks) (void)hipHostFree(L->h_nblocks);
-  if (L->last_write) (void)hipEventDestroy(L->last_write);
+  PinnedBuf<u32> h_nblocks;  // the pinned word and the event go back to owners, which release them here
+  Event last_write;
+  h_nblocks.p = L->h_nblocks;
+  last_write.e = L->last_write;
   delete L;
 }
 
@@ -328,13 +351,12 @@ static int upload_from_device(cox_layer* L, const int32_t* d_idx, const u32* d_s
     st = cox_internal_layer_reserve(L, std::max<u64>(2 * L->capacity, static_cast<u64>(nb0) + n));
     if (st != COX_OK) return st == COX_ERR_OUT_OF_MEMORY ? COX_ERR_POOL_EXHAUSTED : st;
   }
-  u32* d_pool = nullptr;
-  COX_HIP(hipMalloc(reinterpret_cast<void**>(&d_pool), sizeof(u32) * n));
+  DevBuf<u32> d_pool;
+  COX_TRY(d_pool.alloc(n));
   hipLaunchKernelGGL(k_upload_insert, dim3((n + 255) / 256), dim3(256), 0, nullptr, L->ht_keys, L->ht_vals, L->ht_cap - 1, L->block_keys,
-                     L->d_nblocks, static_cast<u32>(L->capacity), L->d_err, d_idx, n, d_pool);
-  hipLaunchKernelGGL(k_upload_copy, dim3(n), dim3(256), 0, nullptr, L->voxels, d_src, static_cast<const u32*>(nullptr), d_pool, action);
+                     L->d_nblocks, static_cast<u32>(L->capacity), L->d_err, d_idx, n, d_pool.p);
+  hipLaunchKernelGGL(k_upload_copy, dim3(n), dim3(256), 0, nullptr, L->voxels, d_src, static_cast<const u32*>(nullptr), d_pool.p, action);
   COX_HIP(hipDeviceSynchronize());
-  (void)hipFree(d_pool);
   u32 nb, err;
   st = layer_read_counters(L, &nb, &err);
   if (st != COX_OK) return st;
@@ -352,20 +374,13 @@ extern "C" int cox_layer_upload(cox_layer_t* L, const int32_t* block_idx_xyz, co
   }
   if (n_blocks == 0) return COX_OK;
   const size_t block_words = static_cast<size_t>(kVoxelsPerBlock) * kWordsPerVoxel;
-  int32_t* d_idx = nullptr;
-  u32* d_src = nullptr;
-  COX_HIP(hipMalloc(reinterpret_cast<void**>(&d_idx), sizeof(int32_t) * 3 * n_blocks));
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_src), sizeof(u32) * block_words * n_blocks);
-  if (e != hipSuccess) {
-    (void)hipFree(d_idx);
-    return COX_ERR_OUT_OF_MEMORY;
-  }
+  DevBuf<int32_t> d_idx;
+  DevBuf<u32> d_src;
+  COX_TRY(d_idx.alloc(3 * n_blocks));
+  if (d_src.alloc(block_words * n_blocks) != COX_OK) return COX_ERR_OUT_OF_MEMORY;
   COX_HIP(hipMemcpy(d_idx, block_idx_xyz, sizeof(int32_t) * 3 * n_blocks, hipMemcpyHostToDevice));
   COX_HIP(hipMemcpy(d_src, voxels_3u32, sizeof(u32) * block_words * n_blocks, hipMemcpyHostToDevice));
-  const int st = upload_from_device(L, d_idx, d_src, static_cast<u32>(n_blocks), action);
-  (void)hipFree(d_idx);
-  (void)hipFree(d_src);
-  return st;
+  return upload_from_device(L, d_idx, d_src, static_cast<u32>(n_blocks), action);
 }
 
 // deserializeMsgToLayer from a message that already sits in HBM (the submap hand-over between GPUs: the wire arrays
@@ -411,40 +426,19 @@ int cox_internal_layer_reserve(cox_layer* L, u64 capacity_blocks) {
   if (st != COX_OK) return st;
   const size_t block_bytes = static_cast<size_t>(kVoxelsPerBlock) * kWordsPerVoxel * sizeof(u32);
   const u32 ht_cap = std::max<u32>(1024, next_pow2(2 * capacity_blocks));
-  u32 *voxels = nullptr, *ht_vals = nullptr, *ht_stamp = nullptr, *ht_ord = nullptr;
-  u64 *ht_keys = nullptr, *block_keys = nullptr;
-  bool ok = hipMalloc(reinterpret_cast<void**>(&voxels), capacity_blocks * block_bytes) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&ht_keys), sizeof(u64) * ht_cap) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&ht_vals), sizeof(u32) * ht_cap) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&ht_stamp), sizeof(u32) * ht_cap) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&ht_ord), sizeof(u32) * ht_cap) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&block_keys), sizeof(u64) * capacity_blocks) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    for (void* q : {static_cast<void*>(voxels), static_cast<void*>(ht_keys), static_cast<void*>(ht_vals), static_cast<void*>(ht_stamp), static_cast<void*>(ht_ord),
-                    static_cast<void*>(block_keys)})
-      if (q) (void)hipFree(q);
-    return COX_ERR_OUT_OF_MEMORY;
-  }
-  if (nb) COX_HIP(hipMemcpy(voxels, L->voxels, nb * block_bytes, hipMemcpyDeviceToDevice));
-  COX_HIP(hipMemset(reinterpret_cast<char*>(voxels) + nb * block_bytes, 0, (capacity_blocks - nb) * block_bytes));
-  if (nb) COX_HIP(hipMemcpy(block_keys, L->block_keys, sizeof(u64) * nb, hipMemcpyDeviceToDevice));
-  COX_HIP(hipMemset(ht_keys, 0xFF, sizeof(u64) * ht_cap));
-  COX_HIP(hipMemset(ht_vals, 0xFF, sizeof(u32) * ht_cap));
-  COX_HIP(hipMemset(ht_stamp, 0, sizeof(u32) * ht_cap));
-  COX_HIP(hipMemset(ht_ord, 0, sizeof(u32) * ht_cap));
+  LayerStorage S;  // the new set until the exchange below; whichever set it holds when this function returns is freed
+  if (S.alloc(capacity_blocks, ht_cap) != COX_OK) return COX_ERR_OUT_OF_MEMORY;
+  if (nb) COX_HIP(hipMemcpy(S.voxels, L->voxels, nb * block_bytes, hipMemcpyDeviceToDevice));
+  COX_HIP(hipMemset(reinterpret_cast<char*>(S.voxels.p) + nb * block_bytes, 0, (capacity_blocks - nb) * block_bytes));
+  if (nb) COX_HIP(hipMemcpy(S.block_keys, L->block_keys, sizeof(u64) * nb, hipMemcpyDeviceToDevice));
+  COX_HIP(hipMemset(S.ht_keys, 0xFF, sizeof(u64) * ht_cap));
+  COX_HIP(hipMemset(S.ht_vals, 0xFF, sizeof(u32) * ht_cap));
+  COX_HIP(hipMemset(S.ht_stamp, 0, sizeof(u32) * ht_cap));
+  COX_HIP(hipMemset(S.ht_ord, 0, sizeof(u32) * ht_cap));
   COX_HIP(hipMemcpy(L->d_nblocks, &nb, sizeof(u32), hipMemcpyHostToDevice));  // also undoes a transient overshoot
-  if (nb) hipLaunchKernelGGL(k_rehash, dim3((nb + 255) / 256), dim3(256), 0, nullptr, block_keys, nb, ht_keys, ht_vals, ht_cap - 1, L->d_err);
+  if (nb) hipLaunchKernelGGL(k_rehash, dim3((nb + 255) / 256), dim3(256), 0, nullptr, S.block_keys.p, nb, S.ht_keys.p, S.ht_vals.p, ht_cap - 1, L->d_err);
   COX_HIP(hipDeviceSynchronize());
-  for (void* q : {static_cast<void*>(L->voxels), static_cast<void*>(L->ht_keys), static_cast<void*>(L->ht_vals), static_cast<void*>(L->ht_stamp),
-                  static_cast<void*>(L->ht_ord), static_cast<void*>(L->block_keys)})
-    (void)hipFree(q);
-  L->voxels = voxels;
-  L->ht_keys = ht_keys;
-  L->ht_vals = ht_vals;
-  L->ht_stamp = ht_stamp;
-  L->ht_ord = ht_ord;
-  L->block_keys = block_keys;
+  S.exchange(L);
   L->capacity = capacity_blocks;
   L->ht_cap = ht_cap;
   L->generation += 1;
@@ -557,12 +551,11 @@ extern "C" int cox_layer_export_dev(cox_layer_t* L, int32_t* block_idx_xyz_dev, 
   std::vector<u32> order(nb);
   for (u32 i = 0; i < nb; ++i) order[i] = i;
   std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return keys[a] < keys[b]; });
-  u32* d_order = nullptr;
-  COX_HIP(hipMalloc(reinterpret_cast<void**>(&d_order), sizeof(u32) * nb));
+  DevBuf<u32> d_order;
+  COX_TRY(d_order.alloc(nb));
   COX_HIP(hipMemcpy(d_order, order.data(), sizeof(u32) * nb, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_export_blocks, dim3(nb), dim3(256), 0, nullptr, L->voxels, L->block_keys, d_order, block_idx_xyz_dev, voxels_3u32_dev);
+  hipLaunchKernelGGL(k_export_blocks, dim3(nb), dim3(256), 0, nullptr, L->voxels, L->block_keys, d_order.p, block_idx_xyz_dev, voxels_3u32_dev);
   COX_HIP(hipDeviceSynchronize());
-  (void)hipFree(d_order);
   return err_bits_to_status(err);
 }
 
@@ -626,19 +619,18 @@ __global__ void __launch_bounds__(256) k_relevant_write(const u32* __restrict__ 
   }
 }
 
-// builds the point list on the device; *d_out (n*5 floats) is hipMalloc'ed for the caller
-static int relevant_points_device(cox_layer* L, float min_w, float max_d, float** d_out, u64* n_out) {
-  *d_out = nullptr;
+// builds the point list on the device: n * 5 floats in *d_out, which stays empty for n == 0
+static int relevant_points_device(cox_layer* L, float min_w, float max_d, DevBuf<float>* d_out, u64* n_out) {
   *n_out = 0;
   u32 nb, err;
   int st = layer_read_counters(L, &nb, &err);
   if (st != COX_OK) return st;
   if (nb == 0) return COX_OK;
-  u32* d_counts = nullptr;
-  u64* d_off = nullptr;
-  COX_HIP(hipMalloc(reinterpret_cast<void**>(&d_counts), sizeof(u32) * nb));
-  COX_HIP(hipMalloc(reinterpret_cast<void**>(&d_off), sizeof(u64) * nb));
-  hipLaunchKernelGGL(k_relevant_count, dim3(nb), dim3(256), 0, nullptr, L->voxels, min_w, max_d, d_counts);
+  DevBuf<u32> d_counts;
+  DevBuf<u64> d_off;
+  COX_TRY(d_counts.alloc(nb));
+  COX_TRY(d_off.alloc(nb));
+  hipLaunchKernelGGL(k_relevant_count, dim3(nb), dim3(256), 0, nullptr, L->voxels, min_w, max_d, d_counts.p);
   std::vector<u32> counts(nb);
   std::vector<u64> keys(nb), off(nb);
   COX_HIP(hipMemcpy(counts.data(), d_counts, sizeof(u32) * nb, hipMemcpyDeviceToHost));
@@ -653,56 +645,39 @@ static int relevant_points_device(cox_layer* L, float min_w, float max_d, float*
   }
   if (run) {
     COX_HIP(hipMemcpy(d_off, off.data(), sizeof(u64) * nb, hipMemcpyHostToDevice));
-    float* d_pts = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_pts), sizeof(float) * 5 * run);
-    if (e != hipSuccess) {
-      (void)hipFree(d_counts);
-      (void)hipFree(d_off);
-      return COX_ERR_OUT_OF_MEMORY;
-    }
-    hipLaunchKernelGGL(k_relevant_write, dim3(nb), dim3(256), 0, nullptr, L->voxels, L->block_keys, d_off, min_w, max_d, L->voxel_size, L->block_size, d_pts);
+    DevBuf<float> d_pts;
+    if (d_pts.alloc(5 * run) != COX_OK) return COX_ERR_OUT_OF_MEMORY;
+    hipLaunchKernelGGL(k_relevant_write, dim3(nb), dim3(256), 0, nullptr, L->voxels, L->block_keys, d_off.p, min_w, max_d, L->voxel_size, L->block_size, d_pts.p);
     COX_HIP(hipDeviceSynchronize());
-    *d_out = d_pts;
+    d_out->swap(d_pts);
   }
   *n_out = run;
-  (void)hipFree(d_counts);
-  (void)hipFree(d_off);
   return COX_OK;
 }
 
 extern "C" int cox_layer_registration_points(cox_layer_t* L, float min_voxel_weight, float max_voxel_distance, float* out, uint64_t cap, uint64_t* n) {
   COX_ENTRY();
   if (!L || !n) return COX_ERR_INVALID_ARG;
-  float* d = nullptr;
+  DevBuf<float> d;
   u64 cnt = 0;
-  int st = relevant_points_device(L, min_voxel_weight, max_voxel_distance, &d, &cnt);
-  if (st != COX_OK) return st;
+  COX_TRY(relevant_points_device(L, min_voxel_weight, max_voxel_distance, &d, &cnt));
   *n = cnt;
   if (out && cnt) {
-    if (cap < cnt) {
-      (void)hipFree(d);
-      return COX_ERR_BUFFER_TOO_SMALL;
-    }
+    if (cap < cnt) return COX_ERR_BUFFER_TOO_SMALL;
     COX_HIP(hipMemcpy(out, d, sizeof(float) * 5 * cnt, hipMemcpyDeviceToHost));
   }
-  if (d) (void)hipFree(d);
   return COX_OK;
 }
 
 extern "C" int cox_regpoints_from_layer(cox_layer_t* L, float min_voxel_weight, float max_voxel_distance, cox_regpoints_t** out) {
   COX_ENTRY();
   if (!L || !out) return COX_ERR_INVALID_ARG;
-  float* d = nullptr;
+  DevBuf<float> d;
   u64 cnt = 0;
-  int st = relevant_points_device(L, min_voxel_weight, max_voxel_distance, &d, &cnt);
-  if (st != COX_OK) return st;
-  cox_regpoints* R = new (std::nothrow) cox_regpoints();
-  if (!R) {
-    if (d) (void)hipFree(d);
-    return COX_ERR_OUT_OF_MEMORY;
-  }
-  R->device = L->device;
-  R->pts = d;
+  COX_TRY(relevant_points_device(L, min_voxel_weight, max_voxel_distance, &d, &cnt));
+  cox_regpoints* R = nullptr;
+  COX_TRY(regpoints_new(L->device, 0, &R));  // an empty set, which takes the list over as it is
+  R->pts = d.release();
   R->n = cnt;
   *out = R;
   return COX_OK;
@@ -835,13 +810,12 @@ static int merge_device_blocks(cox_layer* L, const int32_t* d_idx, const u32* d_
       if (st0 != COX_OK) return st0 == COX_ERR_OUT_OF_MEMORY ? COX_ERR_POOL_EXHAUSTED : st0;
     }
   }
-  u32* d_pool = nullptr;
-  COX_HIP(hipMalloc(reinterpret_cast<void**>(&d_pool), sizeof(u32) * n));
+  DevBuf<u32> d_pool;
+  COX_TRY(d_pool.alloc(n));
   hipLaunchKernelGGL(k_upload_insert, dim3((n + 255) / 256), dim3(256), 0, nullptr, L->ht_keys, L->ht_vals, L->ht_cap - 1, L->block_keys, L->d_nblocks,
-                     static_cast<u32>(L->capacity), L->d_err, d_idx, n, d_pool);
-  hipLaunchKernelGGL(k_upload_copy, dim3(n), dim3(256), 0, nullptr, L->voxels, d_src, d_src_index, d_pool, 1);
+                     static_cast<u32>(L->capacity), L->d_err, d_idx, n, d_pool.p);
+  hipLaunchKernelGGL(k_upload_copy, dim3(n), dim3(256), 0, nullptr, L->voxels, d_src, d_src_index, d_pool.p, 1);
   COX_HIP(hipDeviceSynchronize());
-  (void)hipFree(d_pool);
   return COX_OK;
 }
 
@@ -869,11 +843,10 @@ extern "C" int cox_layer_merge(const cox_layer_t* A_, const float T_B_A[7], cox_
     if (A->voxel_size != B->voxel_size) return COX_ERR_INVALID_ARG;
     std::vector<int32_t> idx(3 * static_cast<size_t>(na));
     for (u32 i = 0; i < na; ++i) unpack_key(keys[i], &idx[3 * i], &idx[3 * i + 1], &idx[3 * i + 2]);
-    int32_t* d_idx = nullptr;
-    COX_HIP(hipMalloc(reinterpret_cast<void**>(&d_idx), sizeof(int32_t) * idx.size()));
+    DevBuf<int32_t> d_idx;
+    COX_TRY(d_idx.alloc(idx.size()));
     COX_HIP(hipMemcpy(d_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice));
     st = merge_device_blocks(B, d_idx, A->voxels, nullptr, na);
-    (void)hipFree(d_idx);
   } else {
     // candidate output blocks (transformLayer): input blocks in (z,y,x) order, a float-stepped box around each transformed centre
     std::sort(keys.begin(), keys.end());
@@ -918,21 +891,16 @@ extern "C" int cox_layer_merge(const cox_layer_t* A_, const float T_B_A[7], cox_
     host_rotate(qi, tvec, rt);
     const RigidParams Tinv{qi[0], qi[1], qi[2], qi[3], -rt[0], -rt[1], -rt[2]};
     const size_t block_words = static_cast<size_t>(kVoxelsPerBlock) * kWordsPerVoxel;
-    int32_t* d_cand = nullptr;
-    u32 *d_tmp = nullptr, *d_has = nullptr;
-    COX_HIP(hipMalloc(reinterpret_cast<void**>(&d_cand), sizeof(int32_t) * cand.size()));
-    COX_HIP(hipMalloc(reinterpret_cast<void**>(&d_has), sizeof(u32) * nc));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_tmp), sizeof(u32) * block_words * nc);
-    if (e != hipSuccess) {
-      (void)hipFree(d_cand);
-      (void)hipFree(d_has);
-      return COX_ERR_OUT_OF_MEMORY;
-    }
+    DevBuf<int32_t> d_cand;
+    DevBuf<u32> d_tmp, d_has;
+    COX_TRY(d_cand.alloc(cand.size()));
+    COX_TRY(d_has.alloc(nc));
+    if (d_tmp.alloc(block_words * nc) != COX_OK) return COX_ERR_OUT_OF_MEMORY;
     COX_HIP(hipMemcpy(d_cand, cand.data(), sizeof(int32_t) * cand.size(), hipMemcpyHostToDevice));
     COX_HIP(hipMemset(d_has, 0, sizeof(u32) * nc));
     COX_HIP(hipMemset(d_tmp, 0, sizeof(u32) * block_words * nc));
     const cox::LayerView AV = layer_view(A);
-    hipLaunchKernelGGL(k_resample_blocks, dim3(nc), dim3(256), 0, nullptr, AV, Tinv, d_cand, B->voxel_size, B->block_size, d_tmp, d_has);
+    hipLaunchKernelGGL(k_resample_blocks, dim3(nc), dim3(256), 0, nullptr, AV, Tinv, d_cand.p, B->voxel_size, B->block_size, d_tmp.p, d_has.p);
     std::vector<u32> has(nc);
     COX_HIP(hipMemcpy(has.data(), d_has, sizeof(u32) * nc, hipMemcpyDeviceToHost));
     std::vector<int32_t> keep_idx;
@@ -944,19 +912,14 @@ extern "C" int cox_layer_merge(const cox_layer_t* A_, const float T_B_A[7], cox_
       }
     const u32 nk = static_cast<u32>(keep_src.size());
     if (nk) {
-      int32_t* d_idx = nullptr;
-      u32* d_srcidx = nullptr;
-      COX_HIP(hipMalloc(reinterpret_cast<void**>(&d_idx), sizeof(int32_t) * keep_idx.size()));
-      COX_HIP(hipMalloc(reinterpret_cast<void**>(&d_srcidx), sizeof(u32) * nk));
+      DevBuf<int32_t> d_idx;
+      DevBuf<u32> d_srcidx;
+      COX_TRY(d_idx.alloc(keep_idx.size()));
+      COX_TRY(d_srcidx.alloc(nk));
       COX_HIP(hipMemcpy(d_idx, keep_idx.data(), sizeof(int32_t) * keep_idx.size(), hipMemcpyHostToDevice));
       COX_HIP(hipMemcpy(d_srcidx, keep_src.data(), sizeof(u32) * nk, hipMemcpyHostToDevice));
       st = merge_device_blocks(B, d_idx, d_tmp, d_srcidx, nk);
-      (void)hipFree(d_idx);
-      (void)hipFree(d_srcidx);
     }
-    (void)hipFree(d_cand);
-    (void)hipFree(d_has);
-    (void)hipFree(d_tmp);
   }
   if (st != COX_OK) return st;
   u32 nb, err;

@@ -280,7 +280,7 @@ uint8_t frame_key(double id) {
 struct cox_meshconv {
   int device = 0;
   float interp_step = 0.2f;
-  hipStream_t stream = nullptr;
+  Stream stream;
   // message (device copies) -- setMesh
   bool has_mesh = false;
   float block_edge_length = 0;
@@ -350,7 +350,7 @@ int cox_meshconv_create(int device, float interpolate_voxel_size, cox_meshconv_t
   auto* C = new cox_meshconv();
   C->device = device;
   C->interp_step = interpolate_voxel_size;
-  if (hipStreamCreateWithFlags(&C->stream, hipStreamNonBlocking) != hipSuccess) {
+  if (C->stream.create() != COX_OK) {
     delete C;
     return COX_ERR_NO_DEVICE;
   }
@@ -364,7 +364,6 @@ void cox_meshconv_destroy(cox_meshconv_t* C) {
   (void)hipStreamSynchronize(C->stream);
   free_mesh(C);
   free_clouds(C);
-  (void)hipStreamDestroy(C->stream);
   delete C;
 }
 

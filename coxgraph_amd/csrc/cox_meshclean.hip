@@ -168,16 +168,6 @@ __global__ void __launch_bounds__(256) k_compact_verts(const float* __restrict__
   }
 }
 
-void drop_arrays(cox_meshconn* C) {
-  if (C->pos) (void)hipFree(C->pos);
-  if (C->nrm) (void)hipFree(C->nrm);
-  if (C->rgb) (void)hipFree(C->rgb);
-  if (C->tri) (void)hipFree(C->tri);
-  C->pos = C->nrm = nullptr;
-  C->rgb = nullptr;
-  C->tri = nullptr;
-}
-
 // The mesh is replaced only once every kernel has run: a failure leaves it as it was.
 int clean_impl(cox_meshconn* C, uint64_t removed[3]) {
   const u32 nv = static_cast<u32>(C->n_vertices), nt = static_cast<u32>(C->n_triangles);
@@ -216,7 +206,8 @@ int clean_impl(cox_meshconn* C, uint64_t removed[3]) {
   const u32 nt2 = hm[2], nv2 = hm[3];
   if (nt2 == 0) {  // nothing survives (no vertex is referenced)
     COX_TRY(finish());
-    drop_arrays(C);
+    C->set_vertices(nullptr, nullptr, nullptr);
+    C->set_triangles(nullptr);
   } else {
     DevBuf<float> opos, onrm;
     DevBuf<uint8_t> orgb;
@@ -228,11 +219,8 @@ int clean_impl(cox_meshconn* C, uint64_t removed[3]) {
     COX_LAUNCH(k_compact_tris, nt, C->tri, keep.p, tpos.p, vpos.p, nt, otri.p);
     COX_LAUNCH(k_compact_verts, nv, C->pos, C->nrm, C->rgb, used.p, vpos.p, nv, opos.p, onrm.p, orgb.p);
     COX_TRY(finish());
-    drop_arrays(C);
-    C->pos = opos.release();
-    C->nrm = onrm.release();
-    C->rgb = orgb.release();
-    C->tri = otri.release();
+    C->set_vertices(opos.release(), onrm.release(), orgb.release());
+    C->set_triangles(otri.release());
   }
   C->n_vertices = nv2;
   C->n_triangles = nt2;
@@ -521,23 +509,17 @@ int cox_meshconn_smooth_taubin(cox_meshconn_t* C, int iterations, float lambda, 
   COX_LAUNCH(k_edge_flags, ne, sort.perm(), eu.p, ev.p, ne, flag.p);
   scan.run(flag.p, fpos.p, ne, nullptr);
   COX_LAUNCH(k_csr_fill, ne, sort.perm(), eu.p, ev.p, flag.p, fpos.p, ne, row_begin.p, row_end.p, col.p);
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess) {
-    if (ev0) (void)hipEventDestroy(ev0);
-    return COX_ERR_NO_DEVICE;
-  }
+  EventPair timed;
+  if (timed.create() != COX_OK) return COX_ERR_NO_DEVICE;
   // 2 * iterations launches back to back: lambda into the second buffer, mu back into the mesh's own
-  (void)hipEventRecord(ev0, nullptr);
+  (void)timed.begin(nullptr);
   for (int it = 0; it < iterations; ++it) {
     COX_LAUNCH(k_taubin_half, nv, C->pos, other.p, row_begin.p, row_end.p, col.p, nv, lambda);
     COX_LAUNCH(k_taubin_half, nv, other.p, C->pos, row_begin.p, row_end.p, col.p, nv, mu);
   }
-  (void)hipEventRecord(ev1, nullptr);
+  (void)timed.end(nullptr);
   const int st = finish();
-  float ms = 0.0f;
-  if (st == COX_OK && kernel_ms && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) *kernel_ms = ms;
-  (void)hipEventDestroy(ev0);
-  (void)hipEventDestroy(ev1);
+  if (st == COX_OK && kernel_ms) (void)timed.elapsed_ms(kernel_ms);
   return st;
 }
 
@@ -626,12 +608,7 @@ int cox_meshconn_simplify_clustering(cox_meshconn_t* C, float cell_size, uint64_
     COX_LAUNCH(k_cluster_avg, nc, C->pos, C->nrm, C->rgb, sort.perm(), start.p, nc, opos.p, onrm.p, orgb.p);
     if (C->n_triangles) COX_LAUNCH(k_reindex, 3 * C->n_triangles, C->tri, 3 * C->n_triangles, cid.p);
     COX_TRY(finish());
-    (void)hipFree(C->pos);
-    (void)hipFree(C->nrm);
-    (void)hipFree(C->rgb);
-    C->pos = opos.release();
-    C->nrm = onrm.release();
-    C->rgb = orgb.release();
+    C->set_vertices(opos.release(), onrm.release(), orgb.release());
     C->n_vertices = nc;
   }
   // 4. no degenerate or duplicate triangle, no unreferenced vertex

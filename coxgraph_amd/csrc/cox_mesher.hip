@@ -446,18 +446,11 @@ int order_behind_frames(cox_layer* L) {
 void free_meshlayer(cox_meshlayer* M) {
   if (!M) return;
   (void)hipSetDevice(M->device);
-  if (M->pos) (void)hipFree(M->pos);
-  if (M->nrm) (void)hipFree(M->nrm);
-  if (M->rgb) (void)hipFree(M->rgb);
   delete M;
 }
 void free_meshconn(cox_meshconn* C) {
   if (!C) return;
   (void)hipSetDevice(C->device);
-  if (C->pos) (void)hipFree(C->pos);
-  if (C->nrm) (void)hipFree(C->nrm);
-  if (C->rgb) (void)hipFree(C->rgb);
-  if (C->tri) (void)hipFree(C->tri);
   delete C;
 }
 
@@ -497,23 +490,15 @@ int cox_meshlayer_from_layer(cox_layer_t* L, float min_weight, cox_meshlayer_t**
     if (int st = d_missing.alloc(1)) return fail(st);
     if (hipMemcpy(d_order.p, order.data(), sizeof(u32) * nb, hipMemcpyHostToDevice) != hipSuccess) return fail(COX_ERR_NO_DEVICE);
     const MeshView V{L->voxels, L->ht_keys, L->ht_vals, L->ht_cap - 1, L->voxel_size, L->voxel_size_inv, L->block_size, L->block_size_inv};
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (auto& e : ev)
-      if (hipEventCreate(&e) != hipSuccess) return fail(COX_ERR_NO_DEVICE);
-    auto drop_events = [&]() {
-      for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-    };
-    (void)hipEventRecord(ev[0], nullptr);
+    EventPair t_count, t_fill;
+    if (t_count.create() != COX_OK || t_fill.create() != COX_OK) return fail(COX_ERR_NO_DEVICE);
+    (void)t_count.begin(nullptr);
     hipLaunchKernelGGL(k_mesh_block<false>, dim3(nb), dim3(256), 0, nullptr, V, d_order.p, L->block_keys, min_weight, d_tris.p,
                        static_cast<const u64*>(nullptr), static_cast<float*>(nullptr), static_cast<float*>(nullptr), static_cast<uint8_t*>(nullptr),
                        static_cast<u32*>(nullptr));
-    (void)hipEventRecord(ev[1], nullptr);
+    (void)t_count.end(nullptr);
     std::vector<u32> tris(nb);
-    if (hipMemcpy(tris.data(), d_tris.p, sizeof(u32) * nb, hipMemcpyDeviceToHost) != hipSuccess) {
-      drop_events();
-      return fail(COX_ERR_NO_DEVICE);
-    }
+    if (hipMemcpy(tris.data(), d_tris.p, sizeof(u32) * nb, hipMemcpyDeviceToHost) != hipSuccess) return fail(COX_ERR_NO_DEVICE);
     // the blocks with triangles, their vertex ranges
     std::vector<u32> live;
     u64 nv = 0;
@@ -530,10 +515,7 @@ int cox_meshlayer_from_layer(cox_layer_t* L, float min_weight, cox_meshlayer_t**
     }
     M->n_blocks = live.size();
     M->n_vertices = nv;
-    if (nv > 0xFFFFFFF0ull) {
-      drop_events();
-      return fail(COX_ERR_UNSUPPORTED);
-    }
+    if (nv > 0xFFFFFFF0ull) return fail(COX_ERR_UNSUPPORTED);
     if (M->n_blocks) {
       int st = COX_OK;
       DevBuf<float> pos, nrm;
@@ -545,30 +527,20 @@ int cox_meshlayer_from_layer(cox_layer_t* L, float min_weight, cox_meshlayer_t**
       if (!st && hipMemcpy(d_order.p, live.data(), sizeof(u32) * live.size(), hipMemcpyHostToDevice) != hipSuccess) st = COX_ERR_NO_DEVICE;
       if (!st && hipMemcpy(d_begin.p, M->vertex_begin.data(), sizeof(u64) * M->n_blocks, hipMemcpyHostToDevice) != hipSuccess) st = COX_ERR_NO_DEVICE;
       if (!st && hipMemsetAsync(d_missing.p, 0, sizeof(u32), nullptr) != hipSuccess) st = COX_ERR_NO_DEVICE;
-      if (st) {
-        drop_events();
-        return fail(st);
-      }
-      (void)hipEventRecord(ev[2], nullptr);
+      if (st) return fail(st);
+      (void)t_fill.begin(nullptr);
       hipLaunchKernelGGL(k_mesh_block<true>, dim3(static_cast<u32>(M->n_blocks)), dim3(256), 0, nullptr, V, d_order.p, L->block_keys, min_weight,
                          static_cast<u32*>(nullptr), d_begin.p, pos.p, nrm.p, rgb.p, d_missing.p);
-      (void)hipEventRecord(ev[3], nullptr);
+      (void)t_fill.end(nullptr);
       u32 miss = 0;
-      if (hipMemcpy(&miss, d_missing.p, sizeof(u32), hipMemcpyDeviceToHost) != hipSuccess) {
-        drop_events();
-        return fail(COX_ERR_NO_DEVICE);
-      }
+      if (hipMemcpy(&miss, d_missing.p, sizeof(u32), hipMemcpyDeviceToHost) != hipSuccess) return fail(COX_ERR_NO_DEVICE);
       M->n_color_missing = miss;
       M->pos = pos.release();
       M->nrm = nrm.release();
       M->rgb = rgb.release();
-      float ms = 0.0f;
-      if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) M->kernel_ms[1] = ms;
+      if (!t_fill.elapsed_ms(&M->kernel_ms[1])) return fail(COX_ERR_NO_DEVICE);
     }
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) M->kernel_ms[0] = ms;
-    drop_events();
-    if (hipGetLastError() != hipSuccess) return fail(COX_ERR_NO_DEVICE);
+    if (!t_count.elapsed_ms(&M->kernel_ms[0]) || hipGetLastError() != hipSuccess) return fail(COX_ERR_NO_DEVICE);
   }
   if (n_blocks) *n_blocks = M->n_blocks;
   if (n_triangles) *n_triangles = M->n_vertices / 3;

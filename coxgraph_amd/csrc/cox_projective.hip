@@ -299,25 +299,23 @@ __global__ void __launch_bounds__(256) k_proj_update(ProjParams P, const u32* __
 struct cox_projective {
   cox_layer* layer = nullptr;
   cox_tsdf_config cfg;
-  hipStream_t stream = nullptr;
-  u32* range = nullptr;
-  u32* touched_slots = nullptr;
-  u64 touched_cap = 0;
-  ProjCounters* cnt = nullptr;
-  ProjCounters* h_cnt = nullptr;  // pinned
-  float* own_xyz = nullptr;
-  u64 xyz_cap = 0;  // floats
+  Stream stream;
+  DevBuf<u32> range;
+  DevBuf<u32> touched_slots;
+  DevBuf<ProjCounters> cnt;
+  PinnedBuf<ProjCounters> h_cnt;
+  DevBuf<float> own_xyz;
   u32 layer_generation = 0;
   cox_frame_stats last{};
   bool pending = false;
-  hipEvent_t ring[4] = {};  // end of the last four frames: at most four are in flight (bounds how old the host's view of the pool is)
+  Event ring[4];  // end of the last four frames: at most four are in flight (bounds how old the host's view of the pool is)
   uint64_t frames = 0;
   u64 blocks_seen = 0, blocks_delta_max = 0;
   // Pool overflow (slow path).  d_stall: 0, or the number (ProjParams::seq) of the first frame that found no pool block; while it
   // is set the device drops every frame whole.  h_stall (pinned): [0] its copy, left by the last kernel of every dropped frame,
   // [1] the pool index that frame's own allocations start at.  The frames that may still be in flight are kept to be enqueued again.
-  u32* d_stall = nullptr;
-  u32* h_stall = nullptr;
+  DevBuf<u32> d_stall;
+  PinnedBuf<u32> h_stall;
   struct Frame {
     float T[7];
     const float* xyz;
@@ -327,7 +325,21 @@ struct cox_projective {
   int deferred = COX_OK;  // what settling on behalf of another writer ended with: reported by this integrator's next call
   // observation record (cox_integrator_attach_history): marks every integrated cloud on its own stream, behind ev_obs
   cox_obs* obs = nullptr;
-  hipEvent_t ev_obs = nullptr;
+  Event ev_obs;
+
+  int acquire(size_t px) {
+    COX_TRY(stream.create());
+    for (Event& e : ring) COX_TRY(e.create(false));
+    COX_TRY(range.alloc(px));
+    COX_TRY(cnt.alloc(1));
+    COX_TRY(h_cnt.alloc(1));
+    COX_TRY(touched_slots.alloc(layer->ht_cap));
+    COX_TRY(d_stall.alloc(1));
+    COX_TRY(h_stall.alloc(2));
+    COX_TRY(cox_hip_status(hipMemset(d_stall, 0, sizeof(u32))));
+    h_stall.p[0] = h_stall.p[1] = 0;
+    return cox_hip_status(hipDeviceSynchronize());
+  }
 };
 
 void cox_proj_destroy(cox_projective* P) {
@@ -338,16 +350,7 @@ void cox_proj_destroy(cox_projective* P) {
     P->layer->settle_writer = nullptr;
     P->layer->settle_ctx = nullptr;
   }
-  for (void* q : {static_cast<void*>(P->range), static_cast<void*>(P->touched_slots), static_cast<void*>(P->cnt), static_cast<void*>(P->own_xyz),
-                  static_cast<void*>(P->d_stall)})
-    if (q) (void)hipFree(q);
-  if (P->h_cnt) (void)hipHostFree(P->h_cnt);
-  if (P->h_stall) (void)hipHostFree(P->h_stall);
-  for (hipEvent_t e : P->ring)
-    if (e) (void)hipEventDestroy(e);
   if (P->obs) (void)cox_internal_obs_wait(P->obs);
-  if (P->ev_obs) (void)hipEventDestroy(P->ev_obs);
-  if (P->stream) (void)hipStreamDestroy(P->stream);
   delete P;
 }
 
@@ -361,18 +364,7 @@ int cox_proj_create(cox_layer* layer, const cox_tsdf_config* cfg, cox_projective
   P->cfg = *cfg;
   P->layer_generation = layer->generation;
   const size_t px = static_cast<size_t>(cfg->sensor_horizontal_resolution) * cfg->sensor_vertical_resolution;
-  bool ok = hipStreamCreateWithFlags(&P->stream, hipStreamNonBlocking) == hipSuccess;
-  for (hipEvent_t& e : P->ring) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&P->range), sizeof(u32) * px) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&P->cnt), sizeof(ProjCounters)) == hipSuccess;
-  ok = ok && hipHostMalloc(reinterpret_cast<void**>(&P->h_cnt), sizeof(ProjCounters), hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&P->touched_slots), sizeof(u32) * layer->ht_cap) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&P->d_stall), sizeof(u32)) == hipSuccess;
-  ok = ok && hipHostMalloc(reinterpret_cast<void**>(&P->h_stall), 2 * sizeof(u32), hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipMemset(P->d_stall, 0, sizeof(u32)) == hipSuccess;
-  if (ok) P->h_stall[0] = P->h_stall[1] = 0;
-  P->touched_cap = layer->ht_cap;
-  if (!ok || hipDeviceSynchronize() != hipSuccess) {
+  if (P->acquire(px) != COX_OK) {
     cox_proj_destroy(P);
     return COX_ERR_NO_DEVICE;
   }
@@ -393,18 +385,18 @@ static inline u32 proj_seq(u64 frames) { return static_cast<u32>(frames % kSeqPe
 //   auto-grow off: (or no memory for a larger pool) the frames stay dropped: COX_ERR_POOL_EXHAUSTED, the layer as before them.
 static int proj_recover(cox_projective* P) {
   cox_layer* L = P->layer;
-  for (int round = 0; P->h_stall[0] != 0u; ++round) {
-    const u32 back = (proj_seq(P->frames) + kSeqPeriod - P->h_stall[0]) % kSeqPeriod;  // frames to redo, oldest first
+  for (int round = 0; P->h_stall.p[0] != 0u; ++round) {
+    const u32 back = (proj_seq(P->frames) + kSeqPeriod - P->h_stall.p[0]) % kSeqPeriod;  // frames to redo, oldest first
     if (back == 0 || back > 4 || round > 32) return COX_ERR_INTERNAL;
     cox_drain_submitters();  // other integrators on this layer: nothing of theirs is in flight while the table is rebuilt
     COX_HIP(hipDeviceSynchronize());
     u32 nb = 0;
     COX_HIP(hipMemcpy(&nb, L->d_nblocks, sizeof(u32), hipMemcpyDeviceToHost));
-    nb = std::min<u32>(std::min<u32>(nb, static_cast<u32>(L->capacity)), P->h_stall[1]);
+    nb = std::min<u32>(std::min<u32>(nb, static_cast<u32>(L->capacity)), P->h_stall.p[1]);
     COX_HIP(hipMemcpy(L->d_nblocks, &nb, sizeof(u32), hipMemcpyHostToDevice));
     COX_HIP(hipMemset(P->d_stall, 0, sizeof(u32)));
-    P->h_stall[0] = 0u;
-    P->h_stall[1] = 0u;
+    P->h_stall.p[0] = 0u;
+    P->h_stall.p[1] = 0u;
     int grown = COX_ERR_POOL_EXHAUSTED;
     if (L->auto_grow && L->capacity < (1ull << 26)) {
       grown = cox_internal_layer_reserve(L, std::min<u64>(2 * L->capacity, 1ull << 26));  // copies nb blocks, rebuilds the table
@@ -433,9 +425,9 @@ static int proj_recover(cox_projective* P) {
 // integrator's frame, and rolling it back would take that frame's blocks with it.  What goes wrong here is this integrator's to report.
 static void proj_settle(void* ctx) {
   cox_projective* P = static_cast<cox_projective*>(ctx);
-  if (!P->pending && P->h_stall[0] == 0u) return;
+  if (!P->pending && P->h_stall.p[0] == 0u) return;
   int st = hipStreamSynchronize(P->stream) == hipSuccess ? COX_OK : COX_ERR_NO_DEVICE;
-  if (st == COX_OK && P->h_stall[0] != 0u) st = proj_recover(P);
+  if (st == COX_OK && P->h_stall.p[0] != 0u) st = proj_recover(P);
   if (st != COX_OK && P->deferred == COX_OK) P->deferred = st;
 }
 static inline int proj_take_deferred(cox_projective* P) {
@@ -448,9 +440,9 @@ static int proj_finish(cox_projective* P) {
   COX_TRY(proj_take_deferred(P));
   COX_HIP(hipStreamSynchronize(P->stream));
   if (P->obs) COX_TRY(cox_internal_obs_wait(P->obs));  // (it reads the frames' clouds)
-  if (P->h_stall[0] != 0u) COX_TRY(proj_recover(P));
+  if (P->h_stall.p[0] != 0u) COX_TRY(proj_recover(P));
   if (P->pending) {
-    const ProjCounters& c = *P->h_cnt;
+    const ProjCounters& c = *P->h_cnt.p;
     u64 sums[3] = {0, 0, 0};
     for (int sh = 0; sh < 64; ++sh)
       for (int k = 0; k < 3; ++k) sums[k] += c.shard[sh][k];
@@ -479,10 +471,9 @@ static int proj_enqueue(cox_projective* P, const float T[7], const float* xyz_de
   hipStream_t s = P->stream;
   // first: a projective integrator that wrote this layer last settles its frames in here, and may grow the layer doing so
   const bool foreign_writer = cox_layer_order_writer(L, P);
-  if (P->layer_generation != L->generation || P->touched_cap < L->ht_cap) {
+  if (P->layer_generation != L->generation || P->touched_slots.cap < L->ht_cap) {
     COX_HIP(hipStreamSynchronize(s));
-    P->touched_cap = 0;  // a new generation gets a new buffer whatever the old one holds
-    COX_TRY(dev_grow(&P->touched_slots, &P->touched_cap, L->ht_cap));
+    COX_TRY(P->touched_slots.alloc(L->ht_cap));  // a new generation gets a new buffer whatever the old one holds
     P->layer_generation = L->generation;
   }
   P->last = cox_frame_stats{};
@@ -558,7 +549,7 @@ int cox_proj_integrate(cox_projective* P, const float T[7], const float* xyz_dev
   // (the first frame of a small pool, a far wall appearing) is dropped whole by the device and redone by proj_recover.
   COX_TRY(proj_take_deferred(P));
   if (P->frames >= 4) COX_HIP(hipEventSynchronize(P->ring[P->frames & 3]));  // frame t-4 is done
-  if (P->h_stall[0] != 0u) {  // pinned word, no synchronisation on the fast path
+  if (P->h_stall.p[0] != 0u) {  // pinned word, no synchronisation on the fast path
     COX_HIP(hipStreamSynchronize(s));
     COX_TRY(proj_recover(P));
   }
@@ -568,7 +559,7 @@ int cox_proj_integrate(cox_projective* P, const float T[7], const float* xyz_dev
   const u64 need = std::max<u64>(2 * n_seen, n_seen + 6 * P->blocks_delta_max);
   if (L->auto_grow && need > L->capacity && L->capacity < (1ull << 26)) {
     COX_HIP(hipStreamSynchronize(s));
-    if (P->h_stall[0] != 0u) COX_TRY(proj_recover(P));
+    if (P->h_stall.p[0] != 0u) COX_TRY(proj_recover(P));
     u64 cap = L->capacity;
     while (cap < need && cap < (1ull << 26)) cap *= 2;
     const int st = cox_internal_layer_reserve(L, std::min<u64>(cap, 1ull << 26));
@@ -590,14 +581,14 @@ int cox_proj_integrate(cox_projective* P, const float T[7], const float* xyz_dev
 
 int cox_proj_attach_history(cox_projective* P, cox_obs* obs) {
   COX_TRY(proj_finish(P));
-  if (obs && !P->ev_obs && hipEventCreateWithFlags(&P->ev_obs, hipEventDisableTiming) != hipSuccess) return COX_ERR_NO_DEVICE;
+  if (obs && !P->ev_obs && P->ev_obs.create(false) != COX_OK) return COX_ERR_NO_DEVICE;
   P->obs = obs;
   return COX_OK;
 }
 
 int cox_proj_integrate_host(cox_projective* P, const float T[7], const float* xyz, uint64_t n, int deintegrate) {
   if (P->pending) COX_TRY(proj_finish(P));  // the staging buffer below is single: the frame that used it last is done
-  COX_TRY(dev_grow(&P->own_xyz, &P->xyz_cap, 3 * n));
+  COX_TRY(P->own_xyz.grow(3 * n));
   if (n) COX_HIP(hipMemcpyAsync(P->own_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, P->stream));
   COX_TRY(cox_proj_integrate(P, T, P->own_xyz, n, deintegrate));
   return proj_finish(P);

@@ -234,33 +234,60 @@ struct cox_reg {
   const cox_regpoints* ref = nullptr;
   const cox_layer* reading = nullptr;
   double no_corr_cost = 0.0;
-  hipStream_t stream = nullptr;
-  u32* d_idx = nullptr;
-  u64 idx_cap = 0;
-  u32* d_stored = nullptr;  // cox_reg_set_samples: indices kept on the GPU, used when a call passes sample_idx == NULL
-  u64 stored_cap = 0, stored_samples = 0;
+  Stream stream;
+  DevBuf<u32> d_idx;
+  DevBuf<u32> d_stored;  // cox_reg_set_samples: indices kept on the GPU, used when a call passes sample_idx == NULL
+  u64 stored_samples = 0;
   bool has_stored = false;
   bool pending = false;    // a cox_reg_normal_eq_begin without its finish
   u64 pending_n = 0;
-  double *d_res = nullptr, *d_jf = nullptr, *d_jr = nullptr;
-  u64 res_cap = 0, jf_cap = 0, jr_cap = 0;
-  u32* d_ticket = nullptr;    // last-workgroup ticket of the fused reduction (zero between launches)
-  double* d_small = nullptr;  // block sums / partials / results
-  u64 small_cap = 0;
-  double* h_small = nullptr;  // pinned, 256 + 2 doubles
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevBuf<double> d_res, d_jf, d_jr;
+  DevBuf<u32> d_ticket;       // last-workgroup ticket of the fused reduction (zero between launches)
+  DevBuf<double> d_small;     // block sums / partials / results
+  PinnedBuf<double> h_small;  // 256 + 2 doubles
+  EventPair ev;
   double ms = 0.0;
   uint64_t launches = 0;
   bool stream_dirty = false;  // work enqueued on this handle's stream that a batch on another handle's stream has to wait for (sample draws / uploads)
   // scratch of cox_reg_normal_eq_batch (owned by the batch's first handle)
-  RegBatchEntry* d_table = nullptr;
-  RegBatchEntry* h_table = nullptr;  // pinned
-  double* d_bpart = nullptr;
-  double* d_bout = nullptr;
-  double* h_bout = nullptr;  // pinned
-  u32* d_btickets = nullptr;
-  u64 batch_cap = 0, bpart_cap = 0;
+  DevBuf<RegBatchEntry> d_table;
+  PinnedBuf<RegBatchEntry> h_table;
+  DevBuf<double> d_bpart, d_bout;
+  PinnedBuf<double> h_bout;
+  DevBuf<u32> d_btickets;
+  u64 batch_cap = 0;  // entries that d_table, h_table, d_bout, h_bout and d_btickets hold: they grow together
+
+  int acquire() {
+    COX_TRY(stream.create());
+    COX_TRY(h_small.alloc(258));
+    COX_TRY(ev.create());
+    COX_TRY(d_ticket.alloc(1));
+    COX_TRY(cox_hip_status(hipMemset(d_ticket, 0, sizeof(u32))));
+    return cox_hip_status(hipDeviceSynchronize());
+  }
+  int grow_batch(u64 cap) {
+    COX_TRY(h_table.grow(cap));
+    COX_TRY(h_bout.grow(kPartial * cap));
+    COX_TRY(d_table.grow(cap));
+    COX_TRY(d_bout.grow(kPartial * cap));
+    return d_btickets.grow(cap);
+  }
 };
+
+// a set of n points on the device, not yet filled; pts stays null for n == 0 (cox_regpoints_data_dev hands it out as it is)
+int regpoints_new(int device, u64 n, cox_regpoints** out) {
+  cox_regpoints* R = new (std::nothrow) cox_regpoints();
+  DevBuf<float> pts;
+  if (!R || (n && pts.alloc(5 * n) != COX_OK)) {
+    delete R;
+    return COX_ERR_OUT_OF_MEMORY;
+  }
+  R->device = device;
+  R->n = n;
+  R->pts = pts.release();
+  *out = R;
+  return COX_OK;
+}
 
 static int stage_samples(cox_reg* G, const uint32_t* sample_idx, uint64_t n_res, const u32** d_idx_out) {
   *d_idx_out = nullptr;
@@ -272,7 +299,7 @@ static int stage_samples(cox_reg* G, const uint32_t* sample_idx, uint64_t n_res,
   if (!sample_idx) return (n_res == G->ref->n) ? COX_OK : COX_ERR_INVALID_ARG;
   for (uint64_t i = 0; i < n_res; ++i)
     if (sample_idx[i] >= G->ref->n) return COX_ERR_INVALID_ARG;
-  COX_TRY(dev_grow(&G->d_idx, &G->idx_cap, n_res));
+  COX_TRY(G->d_idx.grow(n_res));
   COX_HIP(hipMemcpyAsync(G->d_idx, sample_idx, sizeof(u32) * n_res, hipMemcpyHostToDevice, G->stream));
   *d_idx_out = G->d_idx;
   return COX_OK;
@@ -286,20 +313,11 @@ int cox_regpoints_create(int device, const float* xyz_dist_weight, uint64_t n, c
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return COX_ERR_NO_DEVICE;
   COX_HIP(hipSetDevice(device));
-  cox_regpoints* R = new (std::nothrow) cox_regpoints();
-  if (!R) return COX_ERR_OUT_OF_MEMORY;
-  R->device = device;
-  R->n = n;
-  if (n) {
-    if (hipMalloc(reinterpret_cast<void**>(&R->pts), sizeof(float) * 5 * n) != hipSuccess) {
-      delete R;
-      return COX_ERR_OUT_OF_MEMORY;
-    }
-    if (hipMemcpy(R->pts, xyz_dist_weight, sizeof(float) * 5 * n, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(R->pts);
-      delete R;
-      return COX_ERR_NO_DEVICE;
-    }
+  cox_regpoints* R = nullptr;
+  COX_TRY(regpoints_new(device, n, &R));
+  if (n && hipMemcpy(R->pts, xyz_dist_weight, sizeof(float) * 5 * n, hipMemcpyHostToDevice) != hipSuccess) {
+    delete R;
+    return COX_ERR_NO_DEVICE;
   }
   *out = R;
   return COX_OK;
@@ -312,20 +330,11 @@ int cox_regpoints_create_dev(int device, const float* xyz_dist_weight_dev, uint6
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return COX_ERR_NO_DEVICE;
   COX_HIP(hipSetDevice(device));
   COX_HIP(hipDeviceSynchronize());  // whatever produced the buffer is done after this
-  cox_regpoints* R = new (std::nothrow) cox_regpoints();
-  if (!R) return COX_ERR_OUT_OF_MEMORY;
-  R->device = device;
-  R->n = n;
-  if (n) {
-    if (hipMalloc(reinterpret_cast<void**>(&R->pts), sizeof(float) * 5 * n) != hipSuccess) {
-      delete R;
-      return COX_ERR_OUT_OF_MEMORY;
-    }
-    if (hipMemcpy(R->pts, xyz_dist_weight_dev, sizeof(float) * 5 * n, hipMemcpyDeviceToDevice) != hipSuccess) {
-      (void)hipFree(R->pts);
-      delete R;
-      return COX_ERR_NO_DEVICE;
-    }
+  cox_regpoints* R = nullptr;
+  COX_TRY(regpoints_new(device, n, &R));
+  if (n && hipMemcpy(R->pts, xyz_dist_weight_dev, sizeof(float) * 5 * n, hipMemcpyDeviceToDevice) != hipSuccess) {
+    delete R;
+    return COX_ERR_NO_DEVICE;
   }
   *out = R;
   return COX_OK;
@@ -355,20 +364,11 @@ int cox_regpoints_clone_to_device(const cox_regpoints_t* src, int dst_device, co
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || dst_device < 0 || dst_device >= ndev) return COX_ERR_NO_DEVICE;
   COX_HIP(hipSetDevice(dst_device));
-  cox_regpoints* R = new (std::nothrow) cox_regpoints();
-  if (!R) return COX_ERR_OUT_OF_MEMORY;
-  R->device = dst_device;
-  R->n = src->n;
-  if (src->n) {
-    if (hipMalloc(reinterpret_cast<void**>(&R->pts), sizeof(float) * 5 * src->n) != hipSuccess) {
-      delete R;
-      return COX_ERR_OUT_OF_MEMORY;
-    }
-    if (hipMemcpyPeer(R->pts, dst_device, src->pts, src->device, sizeof(float) * 5 * src->n) != hipSuccess) {
-      (void)hipFree(R->pts);
-      delete R;
-      return COX_ERR_NO_DEVICE;
-    }
+  cox_regpoints* R = nullptr;
+  COX_TRY(regpoints_new(dst_device, src->n, &R));
+  if (src->n && hipMemcpyPeer(R->pts, dst_device, src->pts, src->device, sizeof(float) * 5 * src->n) != hipSuccess) {
+    delete R;
+    return COX_ERR_NO_DEVICE;
   }
   *out = R;
   return COX_OK;
@@ -381,8 +381,6 @@ int cox_regpoints_size(const cox_regpoints_t* R, uint64_t* n) {
 void cox_regpoints_destroy(cox_regpoints_t* R) {
   if (!R) return;
   (void)hipSetDevice(R->device);
-  if (R->pts) (void)hipFree(R->pts);
-  if (R->cum) (void)hipFree(R->cum);
   delete R;
 }
 
@@ -397,12 +395,7 @@ int cox_reg_create(const cox_regpoints_t* reference, const cox_layer_t* reading,
   G->ref = reference;
   G->reading = L;
   G->no_corr_cost = cfg ? cfg->no_correspondence_cost : 0.0;
-  bool ok = hipStreamCreateWithFlags(&G->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipHostMalloc(reinterpret_cast<void**>(&G->h_small), sizeof(double) * 258, hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipEventCreate(&G->ev0) == hipSuccess && hipEventCreate(&G->ev1) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&G->d_ticket), sizeof(u32)) == hipSuccess && hipMemset(G->d_ticket, 0, sizeof(u32)) == hipSuccess &&
-       hipDeviceSynchronize() == hipSuccess;
-  if (!ok) {
+  if (G->acquire() != COX_OK) {
     cox_reg_destroy(G);
     return COX_ERR_NO_DEVICE;
   }
@@ -413,15 +406,6 @@ void cox_reg_destroy(cox_reg_t* G) {
   if (!G) return;
   (void)hipSetDevice(G->reading->device);
   if (G->stream) (void)hipStreamSynchronize(G->stream);
-  void* ptrs[] = {G->d_idx, G->d_stored, G->d_res, G->d_jf, G->d_jr, G->d_small, G->d_ticket, G->d_table, G->d_bpart, G->d_bout, G->d_btickets};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (G->h_small) (void)hipHostFree(G->h_small);
-  if (G->h_table) (void)hipHostFree(G->h_table);
-  if (G->h_bout) (void)hipHostFree(G->h_bout);
-  if (G->ev0) (void)hipEventDestroy(G->ev0);
-  if (G->ev1) (void)hipEventDestroy(G->ev1);
-  if (G->stream) (void)hipStreamDestroy(G->stream);
   delete G;
 }
 
@@ -435,28 +419,28 @@ int cox_reg_evaluate(cox_reg_t* G, const double pose_ref[4], const double pose_r
   COX_TRY(stage_samples(G, sample_idx, n_res, &d_idx));
   const u32 n = static_cast<u32>(n_res);
   const u32 nb = (n + kRegThreads - 1) / kRegThreads;
-  COX_TRY(dev_grow(&G->d_res, &G->res_cap, n_res));
-  COX_TRY(dev_grow(&G->d_jf, &G->jf_cap, 4 * n_res));
-  COX_TRY(dev_grow(&G->d_jr, &G->jr_cap, 4 * n_res));
-  COX_TRY(dev_grow(&G->d_small, &G->small_cap, static_cast<u64>(nb) + 2));
+  COX_TRY(G->d_res.grow(n_res));
+  COX_TRY(G->d_jf.grow(4 * n_res));
+  COX_TRY(G->d_jr.grow(4 * n_res));
+  COX_TRY(G->d_small.grow(static_cast<u64>(nb) + 2));
   const RelPose P = make_rel_pose(pose_ref, pose_read);
   hipStream_t s = G->stream;
   cox_layer_wait_writes(G->reading, s);  // frames still in flight on the reading layer
-  COX_HIP(hipEventRecord(G->ev0, s));
+  COX_HIP(G->ev.begin(s));
   hipLaunchKernelGGL(k_reg_evaluate, dim3(nb), dim3(kRegThreads), 0, s, layer_view(G->reading), P, G->ref->pts, d_idx, n, G->no_corr_cost,
-                     residuals ? G->d_res : nullptr, jac_ref ? G->d_jf : nullptr, jac_read ? G->d_jr : nullptr, G->d_small + 2);
+                     residuals ? G->d_res.p : nullptr, jac_ref ? G->d_jf.p : nullptr, jac_read ? G->d_jr.p : nullptr, G->d_small + 2);
   hipLaunchKernelGGL(k_reg_sum_blocks, dim3(1), dim3(64), 0, s, G->d_small + 2, nb, n, G->d_small);
   if (residuals) hipLaunchKernelGGL(k_reg_scale, dim3((n + 255) / 256), dim3(256), 0, s, G->d_res, static_cast<size_t>(n), G->d_small);
   if (jac_ref) hipLaunchKernelGGL(k_reg_scale, dim3((4 * n + 255) / 256), dim3(256), 0, s, G->d_jf, static_cast<size_t>(4) * n, G->d_small);
   if (jac_read) hipLaunchKernelGGL(k_reg_scale, dim3((4 * n + 255) / 256), dim3(256), 0, s, G->d_jr, static_cast<size_t>(4) * n, G->d_small);
-  COX_HIP(hipEventRecord(G->ev1, s));
+  COX_HIP(G->ev.end(s));
   if (residuals) COX_HIP(hipMemcpyAsync(residuals, G->d_res, sizeof(double) * n_res, hipMemcpyDeviceToHost, s));
   if (jac_ref) COX_HIP(hipMemcpyAsync(jac_ref, G->d_jf, sizeof(double) * 4 * n_res, hipMemcpyDeviceToHost, s));
   if (jac_read) COX_HIP(hipMemcpyAsync(jac_read, G->d_jr, sizeof(double) * 4 * n_res, hipMemcpyDeviceToHost, s));
   COX_HIP(hipStreamSynchronize(s));
   COX_HIP(hipGetLastError());
-  float ms = 0.0f;
-  if (hipEventElapsedTime(&ms, G->ev0, G->ev1) == hipSuccess) {
+  double ms = 0.0;
+  if (G->ev.elapsed_ms(&ms)) {
     G->ms += ms;
     G->launches += 1;
   }
@@ -472,7 +456,7 @@ int cox_reg_set_samples(cox_reg_t* G, const uint32_t* sample_idx, uint64_t n_res
   if (!sample_idx) return COX_OK;  // back to "all points in order"
   for (uint64_t i = 0; i < n_res; ++i)
     if (sample_idx[i] >= G->ref->n) return COX_ERR_INVALID_ARG;
-  COX_TRY(dev_grow(&G->d_stored, &G->stored_cap, std::max<uint64_t>(n_res, 1)));
+  COX_TRY(G->d_stored.grow(std::max<uint64_t>(n_res, 1)));
   COX_HIP(hipMemcpy(G->d_stored, sample_idx, sizeof(u32) * n_res, hipMemcpyHostToDevice));
   G->has_stored = true;
   G->stored_samples = n_res;
@@ -489,14 +473,14 @@ int cox_reg_draw_samples(cox_reg_t* G, uint64_t n_res, uint64_t seed) {
   if (R->n == 0) return n_res == 0 ? COX_OK : COX_ERR_INVALID_ARG;
   hipStream_t s = G->stream;
   if (!R->cum) {
-    u64* cum = nullptr;
-    COX_HIP(hipMalloc(reinterpret_cast<void**>(&cum), sizeof(u64) * (R->n + 1)));
-    hipLaunchKernelGGL(k_weight_cumsum, dim3(1), dim3(1024), 0, s, R->pts, R->n, cum, cum + R->n);
-    COX_HIP(hipMemcpyAsync(&R->cum_total, cum + R->n, sizeof(u64), hipMemcpyDeviceToHost, s));
+    DevBuf<u64> cum;
+    COX_TRY(cum.alloc(R->n + 1));
+    hipLaunchKernelGGL(k_weight_cumsum, dim3(1), dim3(1024), 0, s, R->pts, R->n, cum.p, cum.p + R->n);
+    COX_HIP(hipMemcpyAsync(&R->cum_total, cum.p + R->n, sizeof(u64), hipMemcpyDeviceToHost, s));
     COX_HIP(hipStreamSynchronize(s));
-    R->cum = cum;
+    R->cum = cum.release();
   }
-  COX_TRY(dev_grow(&G->d_stored, &G->stored_cap, std::max<uint64_t>(n_res, 1)));
+  COX_TRY(G->d_stored.grow(std::max<uint64_t>(n_res, 1)));
   if (n_res) hipLaunchKernelGGL(k_draw_samples, dim3(static_cast<u32>((n_res + 255) / 256)), dim3(256), 0, s, R->cum, R->n, R->cum_total, seed, G->d_stored, n_res);
   COX_HIP(hipGetLastError());
   G->stream_dirty = true;  // (a batch that runs on another handle's stream waits for the draw)
@@ -531,14 +515,14 @@ int cox_reg_normal_eq_begin(cox_reg_t* G, const double pose_ref[4], const double
   const u32 n = static_cast<u32>(n_res);
   // one workgroup per 256 residuals up to 1024 workgroups (then they stride); the last one to finish reduces
   const u32 nb = std::min<u32>(1024, (n + kRegThreads - 1) / kRegThreads);
-  COX_TRY(dev_grow(&G->d_small, &G->small_cap, static_cast<u64>(nb) * kPartial + kPartial));
+  COX_TRY(G->d_small.grow(static_cast<u64>(nb) * kPartial + kPartial));
   const RelPose P = make_rel_pose(pose_ref, pose_read);
   hipStream_t s = G->stream;
   cox_layer_wait_writes(G->reading, s);  // frames still in flight on the reading layer
-  COX_HIP(hipEventRecord(G->ev0, s));
+  COX_HIP(G->ev.begin(s));
   hipLaunchKernelGGL(k_reg_normal_eq, dim3(nb), dim3(kRegThreads), 0, s, layer_view(G->reading), P, G->ref->pts, d_idx, n, G->no_corr_cost,
                      G->d_small + kPartial, G->d_small, G->d_ticket);
-  COX_HIP(hipEventRecord(G->ev1, s));
+  COX_HIP(G->ev.end(s));
   COX_HIP(hipMemcpyAsync(G->h_small, G->d_small, sizeof(double) * kPartial, hipMemcpyDeviceToHost, s));
   G->pending = true;
   return COX_OK;
@@ -555,8 +539,8 @@ int cox_reg_normal_eq_finish(cox_reg_t* G, double H[64], double b[8], double* co
   COX_HIP(hipSetDevice(G->reading->device));
   COX_HIP(hipStreamSynchronize(G->stream));
   COX_HIP(hipGetLastError());
-  float ms = 0.0f;
-  if (hipEventElapsedTime(&ms, G->ev0, G->ev1) == hipSuccess) {
+  double ms = 0.0;
+  if (G->ev.elapsed_ms(&ms)) {
     G->ms += ms;
     G->launches += 1;
   }
@@ -597,20 +581,9 @@ int cox_reg_normal_eq_batch(cox_reg_t* const* regs, uint64_t n, const double* po
   hipStream_t s = G0->stream;
   if (G0->batch_cap < n) {
     COX_HIP(hipStreamSynchronize(s));
-    if (G0->h_table) (void)hipHostFree(G0->h_table);
-    if (G0->h_bout) (void)hipHostFree(G0->h_bout);
-    for (void* p : {static_cast<void*>(G0->d_table), static_cast<void*>(G0->d_bout), static_cast<void*>(G0->d_btickets)})
-      if (p) (void)hipFree(p);
-    G0->h_table = nullptr, G0->h_bout = nullptr, G0->d_table = nullptr, G0->d_bout = nullptr, G0->d_btickets = nullptr, G0->batch_cap = 0;
+    G0->batch_cap = 0;
     const u64 cap = std::max<u64>(n, 32);
-    if (hipHostMalloc(reinterpret_cast<void**>(&G0->h_table), sizeof(RegBatchEntry) * cap, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&G0->h_bout), sizeof(double) * kPartial * cap, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&G0->d_table), sizeof(RegBatchEntry) * cap) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&G0->d_bout), sizeof(double) * kPartial * cap) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&G0->d_btickets), sizeof(u32) * cap) != hipSuccess) {
-      (void)hipGetLastError();
-      return COX_ERR_OUT_OF_MEMORY;
-    }
+    if (G0->grow_batch(cap) != COX_OK) return COX_ERR_OUT_OF_MEMORY;
     COX_HIP(hipMemset(G0->d_btickets, 0, sizeof(u32) * cap));  // every launch leaves them zero again
     COX_HIP(hipDeviceSynchronize());
     G0->batch_cap = cap;
@@ -621,11 +594,11 @@ int cox_reg_normal_eq_batch(cox_reg_t* const* regs, uint64_t n, const double* po
     const u32 nr = static_cast<u32>(G->has_stored ? G->stored_samples : G->ref->n);
     const u32 nb = std::max<u32>(1, std::min<u32>(1024, (nr + kRegThreads - 1) / kRegThreads));  // (the same partition as a call of its own: same bits)
     nb_max = std::max(nb_max, nb);
-    RegBatchEntry& E = G0->h_table[c];
+    RegBatchEntry& E = G0->h_table.p[c];
     E.L = layer_view(G->reading);
     E.P = make_rel_pose(poses_ref + 4 * c, poses_read + 4 * c);
     E.pts = G->ref->pts;
-    E.sample_idx = G->has_stored ? G->d_stored : nullptr;
+    E.sample_idx = G->has_stored ? G->d_stored.p : nullptr;
     E.no_corr_cost = G->no_corr_cost;
     E.n_res = nr;
     E.nb = nb;
@@ -636,22 +609,22 @@ int cox_reg_normal_eq_batch(cox_reg_t* const* regs, uint64_t n, const double* po
     cox_layer_wait_writes(G->reading, s);  // frames still in flight on the reading layer
   }
   G0->stream_dirty = false;
-  COX_TRY(dev_grow(&G0->d_bpart, &G0->bpart_cap, static_cast<u64>(n) * nb_max * kPartial));
+  COX_TRY(G0->d_bpart.grow(static_cast<u64>(n) * nb_max * kPartial));
   COX_HIP(hipMemcpyAsync(G0->d_table, G0->h_table, sizeof(RegBatchEntry) * n, hipMemcpyHostToDevice, s));
-  COX_HIP(hipEventRecord(G0->ev0, s));
+  COX_HIP(G0->ev.begin(s));
   hipLaunchKernelGGL(k_reg_normal_eq_batch, dim3(nb_max, static_cast<u32>(n)), dim3(kRegThreads), 0, s, G0->d_table, G0->d_bpart, G0->d_bout, G0->d_btickets);
-  COX_HIP(hipEventRecord(G0->ev1, s));
+  COX_HIP(G0->ev.end(s));
   COX_HIP(hipMemcpyAsync(G0->h_bout, G0->d_bout, sizeof(double) * kPartial * n, hipMemcpyDeviceToHost, s));
   COX_HIP(hipStreamSynchronize(s));
   COX_HIP(hipGetLastError());
-  float ms = 0.0f;
-  if (hipEventElapsedTime(&ms, G0->ev0, G0->ev1) == hipSuccess) {
+  double ms = 0.0;
+  if (G0->ev.elapsed_ms(&ms)) {
     G0->ms += ms;
     G0->launches += 1;
   }
   for (uint64_t c = 0; c < n; ++c) {
     const double* D = G0->h_bout + kPartial * c;  // D[row * 16 + col] = sum_p x[row] x[col]
-    const double nr = static_cast<double>(G0->h_table[c].n_res);
+    const double nr = static_cast<double>(G0->h_table.p[c].n_res);
     const double sum_w = D[9 * 16 + 10];
     const double scale = (sum_w > 0.0 && nr > 0.0) ? nr / sum_w : 0.0;
     const double s2 = scale * scale;

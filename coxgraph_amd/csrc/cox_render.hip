@@ -23,14 +23,6 @@ using namespace cox;
 
 namespace {
 
-struct EventPair {  // destroys on scope exit
-  hipEvent_t a = nullptr, b = nullptr;
-  ~EventPair() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-};
-
 constexpr int kRenderThreads = 256;  // 4 waves: 2 x 2 tiles of 8 x 8 pixels
 constexpr int kTile = 16;
 
@@ -259,19 +251,16 @@ int cox_layer_render(cox_layer_t* L, const float T_G_C[7], int w, int h, const f
   uint8_t* d_c = rgba ? buf.p + b_cnt + b_d + b_n : nullptr;
   uint8_t* d_s = status ? buf.p + b_cnt + b_d + b_n + b_c : nullptr;
   EventPair ev;
-  if (stats) {
-    COX_HIP(hipEventCreate(&ev.a));
-    COX_HIP(hipEventCreate(&ev.b));
-  }
+  if (stats) COX_TRY(ev.create());
   hipStream_t s = nullptr;
   cox_layer_wait_writes(L, s);  // frames still in flight on the layer
   if (stats) {
     COX_HIP(hipMemsetAsync(d_cnt, 0, b_cnt, s));
-    COX_HIP(hipEventRecord(ev.a, s));
+    COX_HIP(ev.begin(s));
   }
   launch_render(L, P, d_d, d_n, d_c, d_s, d_cnt, s);
   COX_HIP(hipGetLastError());
-  if (stats) COX_HIP(hipEventRecord(ev.b, s));
+  if (stats) COX_HIP(ev.end(s));
   unsigned long long cnt[4] = {0, 0, 0, 0};
   if (stats) COX_HIP(hipMemcpyAsync(cnt, d_cnt, b_cnt, hipMemcpyDeviceToHost, s));
   if (depth) COX_HIP(hipMemcpyAsync(depth, d_d, b_d, hipMemcpyDeviceToHost, s));
@@ -280,10 +269,8 @@ int cox_layer_render(cox_layer_t* L, const float T_G_C[7], int w, int h, const f
   if (status) COX_HIP(hipMemcpyAsync(status, d_s, n, hipMemcpyDeviceToHost, s));
   COX_HIP(hipStreamSynchronize(s));
   if (stats) {
-    float ms = 0.0f;
-    COX_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+    if (!ev.elapsed_ms(&stats->kernel_ms)) return COX_ERR_NO_DEVICE;
     stats->n_hits = cnt[0], stats->n_samples = cnt[1], stats->n_block_skips = cnt[2], stats->n_budget = cnt[3];
-    stats->kernel_ms = static_cast<double>(ms);
   }
   return COX_OK;
 }

@@ -443,50 +443,70 @@ struct cox_stereo {
   cox_stereo_config cfg{};
   float fB16 = 0.0f;
   bool have_maps = false, have_frame = false, timed = false;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_in = nullptr, ev_read = nullptr;  // the producer's work so far; the frame has read its inputs
-  hipEvent_t ev_t[kStages + 1] = {};
-  float *d_map0 = nullptr, *d_map1 = nullptr;
-  u8 *d_in_left = nullptr, *d_in_right = nullptr;  // staging of cox_stereo_compute
-  u8 *d_rect_left = nullptr, *d_rect_right = nullptr, *d_mask = nullptr;
-  ull *d_census_left = nullptr, *d_census_right = nullptr;
-  u16 *d_S = nullptr, *d_right = nullptr, *d_disparity = nullptr;
-  u32 *d_win = nullptr, *d_counters = nullptr;
-  float* d_depth = nullptr;  // outputs of cox_stereo_compute before they go to the host
-  u8* d_rgba = nullptr;
-  u32* h_counters = nullptr;  // pinned
+  Stream stream;
+  Event ev_in, ev_read;  // the producer's work so far; the frame has read its inputs
+  Event ev_t[kStages + 1];
+  DevBuf<float> d_map0, d_map1;
+  DevBuf<u8> d_in_left, d_in_right;  // staging of cox_stereo_compute
+  DevBuf<u8> d_rect_left, d_rect_right, d_mask;
+  DevBuf<ull> d_census_left, d_census_right;
+  DevBuf<u16> d_S, d_right, d_disparity;
+  DevBuf<u32> d_win, d_counters;
+  DevBuf<float> d_depth;  // outputs of cox_stereo_compute before they go to the host
+  DevBuf<u8> d_rgba;
+  PinnedBuf<u32> h_counters;
   // the filters on the disparity (coxgraph_hip_stereo_filter.h): nothing below exists until one is switched on
   cox_stereo_filter_config fcfg{0, 0, 16, 0};
   bool filter_bufs = false;
   bool last_filtered = false, last_labelled = false;  // of the last frame
   const u16* last_median = nullptr;                   // where the last frame left the image after 7a
-  u16 *f_raw = nullptr, *f_median = nullptr;
-  u32 *f_parent = nullptr, *f_size = nullptr, *f_counters = nullptr;
-  u32* h_fcounters = nullptr;  // pinned
-  hipEvent_t ev_f[3] = {};     // behind step 6, behind 7a, behind 7b
+  DevBuf<u16> f_raw, f_median;
+  DevBuf<u32> f_parent, f_size, f_counters;
+  PinnedBuf<u32> h_fcounters;
+  Event ev_f[3];  // behind step 6, behind 7a, behind 7b
+
+  int acquire(size_t n_px) {
+    COX_TRY(stream.create());
+    COX_TRY(ev_in.create(false));
+    COX_TRY(ev_read.create(false));
+    for (Event& e : ev_t) COX_TRY(e.create(true));
+    if (have_maps) {
+      COX_TRY(d_map0.alloc(2 * n_px));
+      COX_TRY(d_map1.alloc(2 * n_px));
+    }
+    COX_TRY(d_in_left.alloc(n_px));
+    COX_TRY(d_in_right.alloc(n_px));
+    COX_TRY(d_rect_left.alloc(n_px));
+    COX_TRY(d_rect_right.alloc(n_px));
+    COX_TRY(d_mask.alloc(n_px));
+    COX_TRY(d_census_left.alloc(n_px));
+    COX_TRY(d_census_right.alloc(n_px));
+    COX_TRY(d_S.alloc(n_px * static_cast<size_t>(cfg.n_disparities)));
+    COX_TRY(d_right.alloc(n_px));
+    COX_TRY(d_disparity.alloc(n_px));
+    COX_TRY(d_win.alloc(n_px));
+    COX_TRY(d_counters.alloc(kCntWords));
+    COX_TRY(d_depth.alloc(n_px));
+    COX_TRY(d_rgba.alloc(4 * n_px));
+    return h_counters.alloc(kCntWords);
+  }
+  // nothing of it exists until a filter is switched on; what a failed attempt got stays for the next one
+  int acquire_filters(size_t n_px) {
+    for (Event& e : ev_f)
+      if (!e) COX_TRY(e.create(true));
+    if (!f_raw) COX_TRY(f_raw.alloc(n_px));
+    if (!f_median) COX_TRY(f_median.alloc(n_px));
+    if (!f_parent) COX_TRY(f_parent.alloc(n_px));
+    if (!f_size) COX_TRY(f_size.alloc(n_px));
+    if (!f_counters) COX_TRY(f_counters.alloc(cox_stf::kCntWords));
+    if (!h_fcounters) COX_TRY(h_fcounters.alloc(cox_stf::kCntWords));
+    return COX_OK;
+  }
 };
 
 namespace {
 
 size_t n_px_of(const cox_stereo* H) { return static_cast<size_t>(H->w) * H->h; }
-
-void release(cox_stereo* H) {
-  void* bufs[] = {H->d_map0,        H->d_map1,         H->d_in_left, H->d_in_right, H->d_rect_left, H->d_rect_right, H->d_mask,  H->d_census_left,
-                  H->d_census_right, H->d_S,           H->d_right,   H->d_disparity, H->d_win,      H->d_counters,   H->d_depth, H->d_rgba,
-                  H->f_raw,          H->f_median,      H->f_parent,  H->f_size,      H->f_counters};
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
-  if (H->h_counters) (void)hipHostFree(H->h_counters);
-  if (H->h_fcounters) (void)hipHostFree(H->h_fcounters);
-  for (hipEvent_t e : H->ev_f)
-    if (e) (void)hipEventDestroy(e);
-  if (H->ev_in) (void)hipEventDestroy(H->ev_in);
-  if (H->ev_read) (void)hipEventDestroy(H->ev_read);
-  for (hipEvent_t e : H->ev_t)
-    if (e) (void)hipEventDestroy(e);
-  if (H->stream) (void)hipStreamDestroy(H->stream);
-  delete H;
-}
 
 template <int K>
 int launch_paths_and_winner(cox_stereo* H) {
@@ -674,30 +694,7 @@ int cox_stereo_create(int device, int w, int h, const cox_stereo_config* cfg, co
   H->cfg = c;
   H->fB16 = static_cast<float>(static_cast<double>(K_rect[0]) * static_cast<double>(baseline_m) * 16.0);
   H->have_maps = map0_xy != nullptr;
-  bool ok = hipStreamCreateWithFlags(&H->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&H->ev_in, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&H->ev_read, hipEventDisableTiming) == hipSuccess;
-  for (hipEvent_t& e : H->ev_t) ok = ok && hipEventCreate(&e) == hipSuccess;
-  auto dev_alloc = [&ok](auto** p, size_t bytes) { ok = ok && hipMalloc(reinterpret_cast<void**>(p), bytes) == hipSuccess; };
-  if (H->have_maps) {
-    dev_alloc(&H->d_map0, sizeof(float) * 2 * n_px);
-    dev_alloc(&H->d_map1, sizeof(float) * 2 * n_px);
-  }
-  dev_alloc(&H->d_in_left, n_px);
-  dev_alloc(&H->d_in_right, n_px);
-  dev_alloc(&H->d_rect_left, n_px);
-  dev_alloc(&H->d_rect_right, n_px);
-  dev_alloc(&H->d_mask, n_px);
-  dev_alloc(&H->d_census_left, sizeof(ull) * n_px);
-  dev_alloc(&H->d_census_right, sizeof(ull) * n_px);
-  dev_alloc(&H->d_S, sizeof(u16) * n_px * static_cast<size_t>(c.n_disparities));
-  dev_alloc(&H->d_right, sizeof(u16) * n_px);
-  dev_alloc(&H->d_disparity, sizeof(u16) * n_px);
-  dev_alloc(&H->d_win, sizeof(u32) * n_px);
-  dev_alloc(&H->d_counters, sizeof(u32) * kCntWords);
-  dev_alloc(&H->d_depth, sizeof(float) * n_px);
-  dev_alloc(&H->d_rgba, 4 * n_px);
-  ok = ok && hipHostMalloc(reinterpret_cast<void**>(&H->h_counters), sizeof(u32) * kCntWords, hipHostMallocDefault) == hipSuccess;
+  bool ok = H->acquire(n_px) == COX_OK;
   if (ok && H->have_maps) {
     ok = hipMemcpyAsync(H->d_map0, map0_xy, sizeof(float) * 2 * n_px, hipMemcpyHostToDevice, H->stream) == hipSuccess;
     ok = ok && hipMemcpyAsync(H->d_map1, map1_xy, sizeof(float) * 2 * n_px, hipMemcpyHostToDevice, H->stream) == hipSuccess;
@@ -705,7 +702,7 @@ int cox_stereo_create(int device, int w, int h, const cox_stereo_config* cfg, co
   }
   if (!ok) {
     (void)hipGetLastError();
-    release(H);
+    delete H;
     return COX_ERR_OUT_OF_MEMORY;
   }
   *out = H;
@@ -717,7 +714,7 @@ void cox_stereo_destroy(cox_stereo_t* H) {
   COX_ENTRY_NO_DRAIN();
   (void)hipSetDevice(H->device);
   if (H->stream) (void)hipStreamSynchronize(H->stream);  // nothing of this matcher is in flight after this
-  release(H);
+  delete H;
 }
 
 int cox_stereo_compute_dev(cox_stereo_t* H, const uint8_t* left_dev, const uint8_t* right_dev, float* depth_dev, uint8_t* rgba_dev_or_null,
@@ -749,7 +746,7 @@ int cox_stereo_compute(cox_stereo_t* H, const uint8_t* left, const uint8_t* righ
   // the staging buffers are single: in stream order behind the frame that read them last
   COX_HIP(hipMemcpyAsync(H->d_in_left, left, n_px, hipMemcpyHostToDevice, s));
   COX_HIP(hipMemcpyAsync(H->d_in_right, right, n_px, hipMemcpyHostToDevice, s));
-  COX_TRY(enqueue_frame(H, H->d_in_left, H->d_in_right, H->d_depth, rgba_or_null ? H->d_rgba : nullptr, nullptr, false));
+  COX_TRY(enqueue_frame(H, H->d_in_left, H->d_in_right, H->d_depth, rgba_or_null ? H->d_rgba.p : nullptr, nullptr, false));
   COX_HIP(hipMemcpyAsync(depth, H->d_depth, sizeof(float) * n_px, hipMemcpyDeviceToHost, s));
   if (rgba_or_null) COX_HIP(hipMemcpyAsync(rgba_or_null, H->d_rgba, 4 * n_px, hipMemcpyDeviceToHost, s));
   if (disparity_or_null) COX_HIP(hipMemcpyAsync(disparity_or_null, H->d_disparity, sizeof(u16) * n_px, hipMemcpyDeviceToHost, s));
@@ -778,10 +775,10 @@ int cox_stereo_last_stats(cox_stereo_t* H, cox_stereo_stats* out) {
   COX_HIP(hipSetDevice(H->device));
   COX_HIP(hipMemcpyAsync(H->h_counters, H->d_counters, sizeof(u32) * kCntWords, hipMemcpyDeviceToHost, H->stream));
   COX_HIP(hipStreamSynchronize(H->stream));
-  out->n_valid_pixels = H->h_counters[kCntValid];
-  out->n_rejected_uniqueness = H->h_counters[kCntUnique];
-  out->n_rejected_lr = H->h_counters[kCntLr];
-  out->n_rejected_depth = H->h_counters[kCntDepth];
+  out->n_valid_pixels = H->h_counters.p[kCntValid];
+  out->n_rejected_uniqueness = H->h_counters.p[kCntUnique];
+  out->n_rejected_lr = H->h_counters.p[kCntLr];
+  out->n_rejected_depth = H->h_counters.p[kCntDepth];
   if (H->timed) {
     double* stage[kStages] = {&out->remap_ms, &out->census_ms, &out->paths_ms, &out->winner_ms, &out->depth_ms};
     float t = 0.0f;
@@ -839,21 +836,7 @@ int cox_stereo_set_filters(cox_stereo_t* H, const cox_stereo_filter_config* cfg)
   COX_HIP(hipSetDevice(H->device));
   COX_HIP(hipStreamSynchronize(H->stream));
   if ((c.median_size != 0 || c.speckle_window > 0) && !H->filter_bufs) {
-    const size_t n_px = n_px_of(H);
-    bool ok = true;
-    for (hipEvent_t& e : H->ev_f) ok = ok && (e != nullptr || hipEventCreate(&e) == hipSuccess);
-    auto dev_alloc = [&ok](auto** p, size_t bytes) { ok = ok && (*p != nullptr || hipMalloc(reinterpret_cast<void**>(p), bytes) == hipSuccess); };
-    dev_alloc(&H->f_raw, sizeof(u16) * n_px);
-    dev_alloc(&H->f_median, sizeof(u16) * n_px);
-    dev_alloc(&H->f_parent, sizeof(u32) * n_px);
-    dev_alloc(&H->f_size, sizeof(u32) * n_px);
-    dev_alloc(&H->f_counters, sizeof(u32) * cox_stf::kCntWords);
-    ok = ok && (H->h_fcounters != nullptr ||
-                hipHostMalloc(reinterpret_cast<void**>(&H->h_fcounters), sizeof(u32) * cox_stf::kCntWords, hipHostMallocDefault) == hipSuccess);
-    if (!ok) {  // what was allocated stays with the handle for the next attempt; the setting does not change
-      (void)hipGetLastError();
-      return COX_ERR_OUT_OF_MEMORY;
-    }
+    if (H->acquire_filters(n_px_of(H)) != COX_OK) return COX_ERR_OUT_OF_MEMORY;  // the setting does not change
     H->filter_bufs = true;
   }
   H->fcfg = c;
@@ -881,10 +864,10 @@ int cox_stereo_filter_last_stats(cox_stereo_t* H, cox_stereo_filter_stats* out) 
   }
   COX_HIP(hipMemcpyAsync(H->h_fcounters, H->f_counters, sizeof(u32) * cox_stf::kCntWords, hipMemcpyDeviceToHost, H->stream));
   COX_HIP(hipStreamSynchronize(H->stream));
-  out->n_median_changed = H->h_fcounters[cox_stf::kCntMedianChanged];
-  out->n_components = H->h_fcounters[cox_stf::kCntComponents];
-  out->n_speckle_components = H->h_fcounters[cox_stf::kCntSpeckleComponents];
-  out->n_speckle_pixels = H->h_fcounters[cox_stf::kCntSpecklePixels];
+  out->n_median_changed = H->h_fcounters.p[cox_stf::kCntMedianChanged];
+  out->n_components = H->h_fcounters.p[cox_stf::kCntComponents];
+  out->n_speckle_components = H->h_fcounters.p[cox_stf::kCntSpeckleComponents];
+  out->n_speckle_pixels = H->h_fcounters.p[cox_stf::kCntSpecklePixels];
   float t = 0.0f;
   if (hipEventElapsedTime(&t, H->ev_f[0], H->ev_f[1]) == hipSuccess) out->median_ms = t;
   if (hipEventElapsedTime(&t, H->ev_f[1], H->ev_f[2]) == hipSuccess) out->speckle_ms = t;

@@ -461,27 +461,17 @@ int cox_regpoints_from_isosurface(cox_layer_t* L, float min_weight, float vertex
   COX_TRY(sorted_blocks(L, &nb, &keys, &order));
   if (n_mesh_vertices) *n_mesh_vertices = 0;
   if (n_connected_vertices) *n_connected_vertices = 0;
-  cox_regpoints* R = new (std::nothrow) cox_regpoints();
-  if (!R) return COX_ERR_OUT_OF_MEMORY;
-  R->device = L->device;
-  auto fail = [&](int st) {
-    cox_regpoints_destroy(R);
-    return st;
-  };
-  if (nb == 0) {
-    *out = R;
-    return COX_OK;
-  }
+  if (nb == 0) return regpoints_new(L->device, 0, out);
   const TsdfView V = layer_view(L);
   // 1. vertex count per block -> offsets
   DevBuf<u32> bcount;
   DevBuf<u64> boff;
-  if (int st = bcount.alloc(nb)) return fail(st);
-  if (int st = boff.alloc(nb)) return fail(st);
+  if (int st = bcount.alloc(nb)) return st;
+  if (int st = boff.alloc(nb)) return st;
   hipLaunchKernelGGL(k_mc_block<false>, dim3(nb), dim3(256), 0, nullptr, V, order.p, L->block_keys, min_weight, bcount.p, static_cast<const u64*>(nullptr),
                      static_cast<float*>(nullptr));
   std::vector<u32> hcount(nb);
-  if (hipMemcpy(hcount.data(), bcount.p, sizeof(u32) * nb, hipMemcpyDeviceToHost) != hipSuccess) return fail(COX_ERR_NO_DEVICE);
+  if (hipMemcpy(hcount.data(), bcount.p, sizeof(u32) * nb, hipMemcpyDeviceToHost) != hipSuccess) return COX_ERR_NO_DEVICE;
   std::vector<u64> hoff(nb);
   u64 nv = 0;
   for (u32 i = 0; i < nb; ++i) {
@@ -489,25 +479,22 @@ int cox_regpoints_from_isosurface(cox_layer_t* L, float min_weight, float vertex
     nv += hcount[i];
   }
   if (n_mesh_vertices) *n_mesh_vertices = nv;
-  if (nv == 0) {
-    *out = R;
-    return COX_OK;
-  }
-  if (nv > 0x7FFFFFF0ull) return fail(COX_ERR_UNSUPPORTED);
-  if (hipMemcpy(boff.p, hoff.data(), sizeof(u64) * nb, hipMemcpyHostToDevice) != hipSuccess) return fail(COX_ERR_NO_DEVICE);
+  if (nv == 0) return regpoints_new(L->device, 0, out);
+  if (nv > 0x7FFFFFF0ull) return COX_ERR_UNSUPPORTED;
+  if (hipMemcpy(boff.p, hoff.data(), sizeof(u64) * nb, hipMemcpyHostToDevice) != hipSuccess) return COX_ERR_NO_DEVICE;
   // 2. vertices in mesh order
   DevBuf<float> verts, dw;
   DevBuf<u32> vslot, flag, pos, first, misc;
   DevBuf<u64> hkeys;
   const u32 hcap = next_pow2(2 * nv);
-  if (int st = verts.alloc(3 * nv)) return fail(st);
-  if (int st = dw.alloc(2 * nv)) return fail(st);
-  if (int st = vslot.alloc(nv)) return fail(st);
-  if (int st = flag.alloc(nv)) return fail(st);
-  if (int st = pos.alloc(nv)) return fail(st);
-  if (int st = first.alloc(hcap)) return fail(st);
-  if (int st = hkeys.alloc(hcap)) return fail(st);
-  if (int st = misc.alloc(4)) return fail(st);  // [0] error bits, [1] connected vertices, [2] kept vertices
+  if (int st = verts.alloc(3 * nv)) return st;
+  if (int st = dw.alloc(2 * nv)) return st;
+  if (int st = vslot.alloc(nv)) return st;
+  if (int st = flag.alloc(nv)) return st;
+  if (int st = pos.alloc(nv)) return st;
+  if (int st = first.alloc(hcap)) return st;
+  if (int st = hkeys.alloc(hcap)) return st;
+  if (int st = misc.alloc(4)) return st;  // [0] error bits, [1] connected vertices, [2] kept vertices
   hipLaunchKernelGGL(k_mc_block<true>, dim3(nb), dim3(256), 0, nullptr, V, order.p, L->block_keys, min_weight, static_cast<u32*>(nullptr), boff.p, verts.p);
   // 3. merge vertices that share a cell of the proximity grid
   (void)hipMemsetAsync(hkeys.p, 0xFF, sizeof(u64) * hcap, nullptr);
@@ -531,19 +518,20 @@ int cox_regpoints_from_isosurface(cox_layer_t* L, float min_weight, float vertex
   // 4. compact the survivors in mesh order
   ScanWorkspace ws;
   DevBuf<u32> sums;
-  if (int st = sums.alloc(scan_num_blocks(static_cast<u32>(nv)) + 2)) return fail(st);
+  if (int st = sums.alloc(scan_num_blocks(static_cast<u32>(nv)) + 2)) return st;
   ws.block_sums = sums.p;
   exclusive_scan_u32(flag.p, pos.p, nullptr, static_cast<u32>(nv), static_cast<u32>(nv), misc.p + 2, ws, nullptr);
   u32 hm[4] = {0, 0, 0, 0};
-  if (hipMemcpy(hm, misc.p, sizeof(hm), hipMemcpyDeviceToHost) != hipSuccess) return fail(COX_ERR_NO_DEVICE);
-  if (hm[0]) return fail(err_bits_to_status(hm[0]));
+  if (hipMemcpy(hm, misc.p, sizeof(hm), hipMemcpyDeviceToHost) != hipSuccess) return COX_ERR_NO_DEVICE;
+  if (hm[0]) return err_bits_to_status(hm[0]);
   if (n_connected_vertices) *n_connected_vertices = hm[1];
-  R->n = hm[2];
-  if (R->n) {
-    if (hipMalloc(reinterpret_cast<void**>(&R->pts), sizeof(float) * 5 * R->n) != hipSuccess) return fail(COX_ERR_OUT_OF_MEMORY);
-    hipLaunchKernelGGL(k_iso_write, dim3(grid), dim3(256), 0, nullptr, verts.p, nv, flag.p, pos.p, dw.p, R->pts);
+  cox_regpoints* R = nullptr;
+  COX_TRY(regpoints_new(L->device, hm[2], &R));
+  if (R->n) hipLaunchKernelGGL(k_iso_write, dim3(grid), dim3(256), 0, nullptr, verts.p, nv, flag.p, pos.p, dw.p, R->pts);
+  if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) {
+    delete R;
+    return COX_ERR_NO_DEVICE;
   }
-  if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return fail(COX_ERR_NO_DEVICE);
   *out = R;
   return COX_OK;
 }

@@ -302,16 +302,26 @@ bool pose_ok(const float T[7]) {
 struct cox_track {
   const cox_layer* layer = nullptr;
   cox_track_config cfg;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  TrackState* d_state = nullptr;
-  TrackState* h_state = nullptr;  // pinned
-  double* d_partials = nullptr;   // [kTrackMaxGroups][256]
-  double* d_out = nullptr;        // [256]
-  double* h_out = nullptr;        // pinned [256]
-  u32* d_ticket = nullptr;
-  float* d_pts = nullptr;  // staging of cox_track_refine's host points
-  u64 pts_cap = 0;       // floats
+  Stream stream;
+  EventPair ev;
+  DevBuf<TrackState> d_state;
+  PinnedBuf<TrackState> h_state;
+  DevBuf<double> d_partials;  // [kTrackMaxGroups][256]
+  DevBuf<double> d_out;       // [256]
+  PinnedBuf<double> h_out;    // [256]
+  DevBuf<u32> d_ticket;
+  DevBuf<float> d_pts;  // staging of cox_track_refine's host points
+
+  int acquire() {
+    COX_TRY(stream.create());
+    COX_TRY(ev.create());
+    COX_TRY(h_state.alloc(1));
+    COX_TRY(h_out.alloc(kTile));
+    COX_TRY(d_state.alloc(1));
+    COX_TRY(d_partials.alloc(static_cast<size_t>(kTile) * kTrackMaxGroups));
+    COX_TRY(d_out.alloc(kTile));
+    return d_ticket.alloc(1);
+  }
 };
 
 namespace {
@@ -333,14 +343,14 @@ int run_steps(cox_track* K, const float T[7], const ScanView& S, u32 iterations,
   cox_layer_wait_writes(K->layer, s);  // frames still in flight on the layer
   COX_HIP(hipMemsetAsync(K->d_ticket, 0, sizeof(u32), s));  // whatever an earlier, failed launch left behind
   COX_HIP(hipMemcpyAsync(K->d_state, h, sizeof(TrackState), hipMemcpyHostToDevice, s));
-  COX_HIP(hipEventRecord(K->ev0, s));
+  COX_HIP(K->ev.begin(s));
   for (u32 it = 0; it < iterations; ++it) {
     if (c.dof == 6)
       hipLaunchKernelGGL((k_track_step<6>), dim3(nb), dim3(kTrackThreads), 0, s, V, S, C, K->d_state, K->d_partials, K->d_out, K->d_ticket);
     else
       hipLaunchKernelGGL((k_track_step<4>), dim3(nb), dim3(kTrackThreads), 0, s, V, S, C, K->d_state, K->d_partials, K->d_out, K->d_ticket);
   }
-  COX_HIP(hipEventRecord(K->ev1, s));
+  COX_HIP(K->ev.end(s));
   COX_HIP(hipGetLastError());
   COX_HIP(hipMemcpyAsync(h, K->d_state, sizeof(TrackState), hipMemcpyDeviceToHost, s));
   if (want_sums) COX_HIP(hipMemcpyAsync(K->h_out, K->d_out, sizeof(double) * kTile, hipMemcpyDeviceToHost, s));
@@ -350,7 +360,7 @@ int run_steps(cox_track* K, const float T[7], const ScanView& S, u32 iterations,
 
 int refine_scan(cox_track* K, const float T_prior[7], const ScanView& S, float T_refined[7], cox_track_result* result) {
   COX_TRY(run_steps(K, T_prior, S, K->cfg.max_iterations, 1, false));
-  const TrackState& h = *K->h_state;
+  const TrackState& h = *K->h_state.p;
   if (T_refined)
     for (int k = 0; k < 7; ++k) T_refined[k] = static_cast<float>(h.T[k]);
   if (result) {
@@ -361,8 +371,7 @@ int refine_scan(cox_track* K, const float T_prior[7], const ScanView& S, float T
     result->first_cost = h.first_cost, result->last_cost = h.last_cost;
     result->last_step_translation = h.step_t, result->last_step_rotation = h.step_r;
     for (int k = 0; k < 7; ++k) result->T_G_C[k] = h.T[k];
-    float ms = 0.0f;
-    result->kernel_ms = hipEventElapsedTime(&ms, K->ev0, K->ev1) == hipSuccess ? static_cast<double>(ms) : 0.0;
+    if (!K->ev.elapsed_ms(&result->kernel_ms)) result->kernel_ms = 0.0;
   }
   return COX_OK;
 }
@@ -377,7 +386,7 @@ int normal_eq_scan(cox_track* K, const float T[7], const ScanView& S, double H[3
   if (b)
     for (int r = 0; r < 6; ++r) b[r] = r < dof ? D[r * 16 + dof] : 0.0;
   if (cost) *cost = D[dof * 16 + dof];
-  if (counts) counts[0] = K->h_state->last_used, counts[1] = K->h_state->last_considered;
+  if (counts) counts[0] = K->h_state.p->last_used, counts[1] = K->h_state.p->last_considered;
   return COX_OK;
 }
 
@@ -430,16 +439,7 @@ int cox_track_create(const cox_layer_t* layer, const cox_track_config* cfg, cox_
   if (!K) return COX_ERR_OUT_OF_MEMORY;
   K->layer = layer;
   K->cfg = c;
-  bool ok = hipStreamCreateWithFlags(&K->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipEventCreate(&K->ev0) == hipSuccess && hipEventCreate(&K->ev1) == hipSuccess;
-  ok = ok && hipHostMalloc(reinterpret_cast<void**>(&K->h_state), sizeof(TrackState), hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipHostMalloc(reinterpret_cast<void**>(&K->h_out), sizeof(double) * kTile, hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&K->d_state), sizeof(TrackState)) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&K->d_partials), sizeof(double) * kTile * kTrackMaxGroups) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&K->d_out), sizeof(double) * kTile) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&K->d_ticket), sizeof(u32)) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
+  if (K->acquire() != COX_OK) {
     cox_track_destroy(K);
     return COX_ERR_NO_DEVICE;
   }
@@ -451,14 +451,6 @@ void cox_track_destroy(cox_track_t* K) {
   if (!K) return;
   (void)hipSetDevice(K->layer->device);
   if (K->stream) (void)hipStreamSynchronize(K->stream);
-  void* ptrs[] = {K->d_state, K->d_partials, K->d_out, K->d_ticket, K->d_pts};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (K->h_state) (void)hipHostFree(K->h_state);
-  if (K->h_out) (void)hipHostFree(K->h_out);
-  if (K->ev0) (void)hipEventDestroy(K->ev0);
-  if (K->ev1) (void)hipEventDestroy(K->ev1);
-  if (K->stream) (void)hipStreamDestroy(K->stream);
   delete K;
 }
 
@@ -517,7 +509,7 @@ int cox_track_refine(cox_track_t* K, const float T_prior[7], const float* xyz, u
   COX_TRY(device_present());
   if (!K || !T_prior || !pose_ok(T_prior) || (n && !xyz) || n > 0x7FFFFFFFull) return COX_ERR_INVALID_ARG;
   COX_HIP(hipSetDevice(K->layer->device));
-  COX_TRY(dev_grow(&K->d_pts, &K->pts_cap, 3 * n));
+  COX_TRY(K->d_pts.grow(3 * n));
   if (n) COX_HIP(hipMemcpyAsync(K->d_pts, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, K->stream));
   ScanView S;
   COX_TRY(points_view(K->d_pts, n, K->cfg.stride, &S));

@@ -433,20 +433,23 @@ struct cox_viewgain {
   cox_viewgain_config cfg;
   GainParams P;
   u64 workspace_bytes = 0, slot_bytes = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  float* d_rays = nullptr;  // [h][w][3] dir_C
-  u32* d_bitmap = nullptr;
-  u64 bitmap_words = 0;
-  ViewInfo* d_info = nullptr;
-  u64 info_cap = 0;
-  ull* d_counters = nullptr;
-  u64 counters_cap = 0;  // in words
-  ull* d_totals = nullptr;  // T_WORDS, then the visible set's size
-  float* d_poses = nullptr;  // staging of the host entry points
-  u64 poses_cap = 0;
-  cox_view_gain* d_out = nullptr;
-  u64 out_cap = 0;
+  Stream stream;
+  EventPair ev;
+  DevBuf<float> d_rays;  // [h][w][3] dir_C
+  DevBuf<u32> d_bitmap;
+  DevBuf<ViewInfo> d_info;
+  DevBuf<ull> d_counters;
+  DevBuf<ull> d_totals;   // T_WORDS, then the visible set's size
+  DevBuf<float> d_poses;  // staging of the host entry points
+  DevBuf<cox_view_gain> d_out;
+
+  int acquire(const std::vector<float>& rays) {
+    COX_TRY(stream.create());
+    COX_TRY(ev.create());
+    COX_TRY(d_rays.alloc(rays.size()));
+    COX_TRY(d_totals.alloc(T_WORDS + 1));
+    return cox_hip_status(hipMemcpy(d_rays, rays.data(), rays.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
 };
 
 namespace {
@@ -461,9 +464,9 @@ int enqueue_views(cox_viewgain* H, const float* poses_dev, u64 n, cox_view_gain*
   if (per_chunk > grid_cap) per_chunk = grid_cap;
   if (per_chunk > n) per_chunk = n;
   if (per_chunk == 0) return COX_ERR_INVALID_ARG;  // more tiles in one view than a grid holds
-  COX_TRY(dev_grow(&H->d_bitmap, &H->bitmap_words, per_chunk * P.slot_words));
-  COX_TRY(dev_grow(&H->d_info, &H->info_cap, n));
-  COX_TRY(dev_grow(&H->d_counters, &H->counters_cap, n * C_WORDS));
+  COX_TRY(H->d_bitmap.grow(per_chunk * P.slot_words));
+  COX_TRY(H->d_info.grow(n));
+  COX_TRY(H->d_counters.grow(n * C_WORDS));
   const LayerView V = layer_view(H->layer);  // read on every call: a layer that grew has new buffers
   cox_layer_wait_writes(H->layer, s);        // frames still in flight on the layer
   hipLaunchKernelGGL(k_vg_prep, dim3(static_cast<u32>(n)), dim3(kThreads), 0, s, V, P, H->d_rays, poses_dev, H->d_info, H->d_counters);
@@ -553,13 +556,7 @@ int cox_viewgain_create(cox_layer_t* layer, const cox_viewgain_config* cfg, cox_
       float* r = &rays[3 * (static_cast<size_t>(v) * c.w + u)];
       r[0] = x / n, r[1] = y / n, r[2] = 1.0f / n;
     }
-  bool ok = hipStreamCreateWithFlags(&H->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipEventCreate(&H->ev0) == hipSuccess && hipEventCreate(&H->ev1) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&H->d_rays), rays.size() * sizeof(float)) == hipSuccess;
-  ok = ok && hipMalloc(reinterpret_cast<void**>(&H->d_totals), (T_WORDS + 1) * sizeof(ull)) == hipSuccess;
-  ok = ok && hipMemcpy(H->d_rays, rays.data(), rays.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
+  if (H->acquire(rays) != COX_OK) {
     cox_viewgain_destroy(H);
     return COX_ERR_NO_DEVICE;
   }
@@ -571,12 +568,6 @@ void cox_viewgain_destroy(cox_viewgain_t* H) {
   if (!H) return;
   (void)hipSetDevice(H->layer->device);
   if (H->stream) (void)hipStreamSynchronize(H->stream);
-  void* ptrs[] = {H->d_rays, H->d_bitmap, H->d_info, H->d_counters, H->d_totals, H->d_poses, H->d_out};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (H->ev0) (void)hipEventDestroy(H->ev0);
-  if (H->ev1) (void)hipEventDestroy(H->ev1);
-  if (H->stream) (void)hipStreamDestroy(H->stream);
   delete H;
 }
 
@@ -591,15 +582,15 @@ int cox_viewgain_evaluate(cox_viewgain_t* H, const float* T_G_C, uint64_t n_view
   for (u64 i = 0; i < n_views; ++i)
     if (!finite_all(T_G_C + 7 * i, 7)) return COX_ERR_INVALID_ARG;
   COX_HIP(hipSetDevice(H->layer->device));
-  COX_TRY(dev_grow(&H->d_poses, &H->poses_cap, 7 * n_views));
-  COX_TRY(dev_grow(&H->d_out, &H->out_cap, n_views));
+  COX_TRY(H->d_poses.grow(7 * n_views));
+  COX_TRY(H->d_out.grow(n_views));
   hipStream_t s = H->stream;
   COX_HIP(hipMemcpyAsync(H->d_poses, T_G_C, sizeof(float) * 7 * n_views, hipMemcpyHostToDevice, s));
   COX_HIP(hipMemsetAsync(H->d_totals, 0, T_WORDS * sizeof(ull), s));
-  COX_HIP(hipEventRecord(H->ev0, s));
+  COX_HIP(H->ev.begin(s));
   u64 n_chunks = 0;
   COX_TRY(enqueue_views(H, H->d_poses, n_views, H->d_out, H->d_totals, s, &n_chunks));
-  COX_HIP(hipEventRecord(H->ev1, s));
+  COX_HIP(H->ev.end(s));
   ull totals[T_WORDS] = {0, 0, 0, 0};
   COX_HIP(hipMemcpyAsync(totals, H->d_totals, sizeof(totals), hipMemcpyDeviceToHost, s));
   COX_HIP(hipStreamSynchronize(s));
@@ -607,8 +598,7 @@ int cox_viewgain_evaluate(cox_viewgain_t* H, const float* T_G_C, uint64_t n_view
   if (totals[T_OVERFLOW]) return COX_ERR_OUT_OF_MEMORY;
   COX_HIP(hipMemcpy(out, H->d_out, sizeof(cox_view_gain) * n_views, hipMemcpyDeviceToHost));
   if (stats) {
-    float ms = 0.0f;
-    stats->kernel_ms = hipEventElapsedTime(&ms, H->ev0, H->ev1) == hipSuccess ? static_cast<double>(ms) : 0.0;
+    if (!H->ev.elapsed_ms(&stats->kernel_ms)) stats->kernel_ms = 0.0;
     stats->n_samples = totals[T_SAMPLES];
     stats->n_chunks = n_chunks;
   }
@@ -630,7 +620,7 @@ int cox_viewgain_visible(cox_viewgain_t* H, const float T_G_C[7], uint64_t cap, 
   COX_TRY(device_present());
   if (!H || !T_G_C || !n || !finite_all(T_G_C, 7)) return COX_ERR_INVALID_ARG;
   COX_HIP(hipSetDevice(H->layer->device));
-  COX_TRY(dev_grow(&H->d_poses, &H->poses_cap, 7));
+  COX_TRY(H->d_poses.grow(7));
   hipStream_t s = H->stream;
   COX_HIP(hipMemcpyAsync(H->d_poses, T_G_C, sizeof(float) * 7, hipMemcpyHostToDevice, s));
   COX_TRY(enqueue_views(H, H->d_poses, 1, nullptr, nullptr, s, nullptr));

@@ -311,7 +311,8 @@ def hostutil_smoke(tmp_path_factory):
 
 def test_host_helpers_without_a_device(hip, hostutil_smoke):
     """Status mapping, COX_TRY, finite_all and no-op growth everywhere; where there is no device also the failure paths of
-    device_present, dev_alloc, dev_grow and DevBuf: the status, a null pointer, a capacity of 0 and no HIP error left behind."""
+    device_present, dev_alloc, dev_grow, DevBuf, PinnedBuf, Stream, Event and EventPair: the status, a null object, a capacity of 0 and no HIP
+    error left behind.  Moves and swaps hand over pointer and capacity and leave the source null."""
     out = subprocess.run([hostutil_smoke], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert out.stdout.split() == ["device" if hip.device_count() > 0 else "no-device"]
@@ -319,6 +320,35 @@ def test_host_helpers_without_a_device(hip, hostutil_smoke):
 
 @pytest.mark.gpu
 def test_host_helpers_grow_on_the_gpu(hostutil_smoke):
-    """0 -> 16 -> 16 -> 17 -> 4 elements: a new buffer at the first and third step only, capacities 16, 16, 17, 17."""
+    """0 -> 16 -> 16 -> 17 -> 4 elements in device and in pinned memory: a new buffer at the first and third step only, capacities
+    16, 16, 17, 17.  An owner that leaves scope frees its buffer, swapped buffers keep their contents, and an EventPair around a
+    memset on a Stream reads a finite time."""
     out = subprocess.run([hostutil_smoke, "gpu"], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
+
+
+def test_runtime_resources_are_made_and_released_in_one_place():
+    """Device memory, pinned memory, streams and events come from the owning types of cox_host.hpp (and, for the integrator, from its
+    own owner): no other unit calls the runtime's allocation, stream or event functions, and nothing is freed by hand except a layer's
+    buffers in cox_layer_destroy and what the handles of cox_internal.hpp free in their destructors."""
+    import glob
+    import re
+    csrc = os.path.join(ROOT, "coxgraph_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp")))
+    assert len(files) > 20
+    src = {os.path.basename(f): open(f).read() for f in files}
+    owners = {"cox_host.hpp", "cox_integrator.hip"}
+    for call in ("hipMalloc(", "hipHostMalloc(", "hipHostFree(", "hipStreamCreateWithFlags(", "hipStreamDestroy(", "hipEventCreate", "hipEventDestroy("):
+        users = {name for name, text in src.items() if call in text}
+        assert users <= owners, (call, sorted(users - owners))
+    users = {name for name, text in src.items() if "hipFree(" in text}
+    assert users <= owners | {"cox_layer.hip", "cox_internal.hpp"}, sorted(users)
+    layer = src["cox_layer.hip"]
+    destroy = re.search(r"\nvoid cox_layer_destroy\(.*?\n}\n", layer, re.S)
+    assert destroy and layer.count("hipFree(") == destroy.group(0).count("hipFree(") > 0
+    everything = "\n".join(src.values())
+    assert everything.count("struct EventPair") == 1 and "struct EventPair" in src["cox_host.hpp"]
+    assert "pinned_grow" not in everything
+    assert everything.count("hipEventElapsedTime(") == sum(src[n].count("hipEventElapsedTime(") for n in ("cox_host.hpp", "cox_integrator.hip", "cox_stereo.hip", "cox_depthfuse.hip"))
+    settle = re.search(r"\nvoid settle_timing\(.*?\n}\n", src["cox_collide.hip"], re.S)
+    assert settle and "hipEventElapsedTime" not in settle.group(0) and "elapsed_ms" in settle.group(0)
