@@ -319,6 +319,14 @@ class Layer(_Handle):
         assert vox.shape == (idx.shape[0], VOXELS_PER_BLOCK, 3)
         self._call("layer_upload", _fp(idx), _fp(vox), C.c_uint64(idx.shape[0]), C.c_int(action))
 
+    def compare(self, other, T=None, ignore="all", sample="nearest", **cfg):
+        """This layer as the test layer against `other` as the reference: the records of LayerComparer(...).run(T, ignore, sample)."""
+        cmp = LayerComparer(self.eng, self, other, **cfg)
+        try:
+            return cmp.run(T, ignore, sample)
+        finally:
+            cmp.close()
+
     # ---- map queries (include/coxgraph_hip_map.h) ----
     def query(self, xyz, mode="interpolate", gradient=False):
         """voxblox Interpolator / EsdfMap batch queries at float32 points [n,3] in the layer's frame (cox_layer_query):
@@ -1811,6 +1819,102 @@ class SubmapAligner(_Handle):
         """(milliseconds of the sweeps' kernels, sweeps) since creation or the last reset."""
         ms, n = C.c_double(), C.c_uint64()
         self._call("align_kernel_time", C.byref(ms), C.byref(n), C.c_int(int(reset)))
+        return float(ms.value), int(n.value)
+
+
+# ---- comparing two layers (include/coxgraph_hip_compare.h, DESIGN.md section 7p) -----------------
+COMPARE_MAX_TRANSFORMS, COMPARE_HIST_BINS, COMPARE_Q_PER_METRE, COMPARE_Q_SATURATED = 1024, 22, 65536, 1 << 20
+COMPARE_IGNORE = {"all": 0, "behind_test": 1, "behind_gt": 2, "behind_all": 3}  # cox_compare_ignore (voxblox VoxelEvaluationMode)
+COMPARE_SAMPLE = {"nearest": 0, "trilinear": 1}                                  # cox_compare_sample
+COMPARE_COUNTS = ("n_a_observed", "n_overlap", "n_ignored", "n_evaluated", "sum_q", "sum_q2_lo", "sum_q2_hi", "n_near_a", "n_near_b",
+                  "n_a_surface_in_b_free", "n_b_surface_in_a_free", "n_agree")
+# classes in the colour word of an error layer
+COMPARE_UNOBSERVED, COMPARE_NO_COUNTERPART, COMPARE_IGNORED, COMPARE_EVALUATED, COMPARE_A_IN_B_FREE, COMPARE_B_IN_A_FREE = 0, 1, 2, 3, 4, 8
+
+
+class CompareConfig(C.Structure):
+    """cox_compare_config."""
+    _fields_ = [("surface_distance", C.c_float), ("free_distance", C.c_float), ("agree_distance", C.c_float), ("min_weight", C.c_float)]
+
+
+class CompareStats(C.Structure):
+    """cox_compare_stats."""
+    _fields_ = [(n, C.c_uint64) for n in COMPARE_COUNTS] + [("hist", C.c_uint64 * COMPARE_HIST_BINS), ("min_q", C.c_uint32), ("max_q", C.c_uint32)]
+
+
+COMPARE_STATS_DTYPE = np.dtype([(n, np.uint64) for n in COMPARE_COUNTS] + [("hist", np.uint64, (COMPARE_HIST_BINS,)), ("min_q", np.uint32), ("max_q", np.uint32)])
+assert COMPARE_STATS_DTYPE.itemsize == 280 == C.sizeof(CompareStats)
+
+
+def compare_config(eng, **cfg):
+    """cox_compare_config_default with overrides (a distance of 0 stands for its default)."""
+    return _config(eng, CompareConfig, "compare_config_default", cfg)
+
+
+def compare_rmse(rec):
+    """The root mean square of |e| in metres from one record: sqrt((hi * 2^20 + lo) / n_evaluated) / 65536, the sum in Python
+    integers and the rest in float64.  NaN when nothing was evaluated."""
+    n = int(rec["n_evaluated"])
+    if n == 0:
+        return float("nan")
+    total = (int(rec["sum_q2_hi"]) << 20) + int(rec["sum_q2_lo"])
+    return float(np.sqrt(np.float64(total) / np.float64(n)) / np.float64(COMPARE_Q_PER_METRE))
+
+
+def compare_conflict_ratio(rec):
+    """(n_a_surface_in_b_free + n_b_surface_in_a_free) / (n_near_a + n_near_b); NaN when no overlapping voxel is near a surface."""
+    den = int(rec["n_near_a"]) + int(rec["n_near_b"])
+    return (int(rec["n_a_surface_in_b_free"]) + int(rec["n_b_surface_in_a_free"])) / den if den else float("nan")
+
+
+def _transforms(T):
+    """None, one pose [7] or poses [n,7] as (contiguous float32 [n,7] or None, n)."""
+    if T is None:
+        return None, 1
+    T = np.ascontiguousarray(T, np.float32)
+    if T.ndim == 1:
+        T = T.reshape(1, -1)
+    assert T.ndim == 2 and T.shape[1] == 7
+    return T, len(T)
+
+
+class LayerComparer(_Handle):
+    """Compares test layer A against reference layer B (cox_compare_t): cfg are fields of cox_compare_config."""
+    _destroy = "compare_destroy"
+
+    def _guard(self, name):
+        """As _Handle._guard with _borrows = ("A", "B")."""
+        if not self.A.h or not self.B.h:
+            raise CoxError(-1, name + " (the layer is closed)")
+        return self.h
+
+    def __init__(self, eng, A, B, **cfg):
+        self.eng, self.A, self.B = eng, A, B
+        asked = compare_config(eng, **cfg)
+        self.h = C.c_void_p()
+        eng.call("compare_create", A.h, B.h, C.byref(asked), C.byref(self.h))
+        self.cfg = CompareConfig()
+        self._call("compare_get_config", C.byref(self.cfg))
+
+    def run(self, T=None, ignore="all", sample="nearest"):
+        """cox_compare_run: one record of COMPARE_STATS_DTYPE per transform T_B_A ([7] or [n,7]); None: the same-frame compare."""
+        T, n = _transforms(T)
+        out = np.zeros(n, COMPARE_STATS_DTYPE)
+        self._call("compare_run", _opt(T), C.c_uint64(n), C.c_int(COMPARE_IGNORE[ignore]), C.c_int(COMPARE_SAMPLE[sample]), _fp(out))
+        return out
+
+    def error_layer(self, T=None, ignore="all", sample="nearest"):
+        """cox_compare_error_layer: a new Layer with A's blocks: distance = e, weight = 1 where evaluated, colour word = class."""
+        T, n = _transforms(T)
+        assert n == 1
+        out = Layer._adopt(self.eng, C.c_void_p(), voxel_size=self.A.voxel_size)
+        self._call("compare_error_layer", _opt(T), C.c_int(COMPARE_IGNORE[ignore]), C.c_int(COMPARE_SAMPLE[sample]), C.byref(out.h))
+        return out
+
+    def kernel_time(self, reset=False):
+        """(milliseconds of the compare kernels, calls that ran one) since creation or the last reset."""
+        ms, n = C.c_double(), C.c_uint64()
+        self._call("compare_kernel_time", C.byref(ms), C.byref(n), C.c_int(int(reset)))
         return float(ms.value), int(n.value)
 
 
